@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpixels/s at 1920x1080, 4x AA, depth 5, 64 spheres (C2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
-                    [--workload c2|c4] [--emulate-rank k/N] [--no-projection] [--inflight F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                    [--workload c2|c4] [--emulate-rank k/N] [--inflight F]
+                    [--no-cpu-baseline] [--no-projection]        (the last two: parts of --full)
+
+A plain run sets up, warms up, times the K steps, writes the last timed
+frame if `--dump-outputs DIR` is given (DIR/frame.npy, float64; a frame above
+60 MB as a fixed seeded sample of its pixels, with DIR/frame_index.npy) and
+prints the result line: the headline figure and its configuration.  `--full`
+adds everything else this file measures or checks, each in runs of its own
+outside the timed region: the CPU baseline, the fixture parity of the last
+timed frame, the gather check and per-rank breakdown of the multi-GPU step,
+one frame's latency, the dominant kernel's time and the roofline, the work
+counts and the 1-GPU projection of the tile-sharded frame.
 
 One step = one complete C2 frame (BASELINE.json configs[2]): 1920x1080 pixels,
 Camera#render_at with pre = max = 4 samples, trace_depth 5, 64 spheres + ground
@@ -25,10 +36,11 @@ replacement of camera.rb:41-68 / fork_jobs.rb:1-33) and gathered to rank 0
 with ONE RCCL gather per frame: strong scaling of the C2 frame.
 
 `--emulate-rank k/N` times rank k's share of an N-rank frame on one GPU;
-the default 1-GPU run also reports `projection`: every rank's share for
+the 1-GPU `--full` run also reports `projection`: every rank's share for
 N = 2, 4, 8 timed on this GPU, the max over ranks, and the projected speedup.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` and the run's configuration; with `--full` also
 `roofline` (FP64 VALU: hardware FP64 rate from the committed PMC pass of this
 kernel build vs 78.6 TF; measured HBM traffic; the reference-work rate and the
 HBM-write fraction beside it) and `cpu_baseline` (the C restatement of the
@@ -142,6 +154,28 @@ def fixture_parity(frame, workload):
             "pass": bool((rms <= 1e-4).all())}
 
 
+DUMP_MAX_BYTES = 60 * 1000 * 1000          # all files of one --dump-outputs stay below 64 MB
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: what the timed path computed in its last step, the frame
+    its caller receives (rows x W x 3 binary64, torch, device), as
+    DIR/frame.npy.  A larger frame than DUMP_MAX_BYTES is written as a fixed
+    sample of its pixels (seeded: the same pixels for every run of one frame
+    size): DIR/frame.npy holds their (n, 3) values and DIR/frame_index.npy
+    their flat pixel indices y * W + x (as float64, exact)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = frame.cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        px = a.shape[0] * a.shape[1]
+        n = DUMP_MAX_BYTES // (a.shape[2] * 8 + 8)       # per pixel: its values and its index
+        idx = np.sort(np.random.default_rng(0).choice(px, size=n, replace=False))
+        np.save(os.path.join(dirname, "frame_index.npy"), idx.astype(np.float64))
+        a = a.reshape(px, a.shape[2])[idx]
+    np.save(os.path.join(dirname, "frame.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launch_ranks(args):
     """--gpus N > 1 without torch.distributed.run: start the N ranks as a child
     torch.distributed.run (this process never touches the GPU) and return its status."""
@@ -212,8 +246,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-projection", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed frame to DIR/frame.npy (float64; a frame "
+                         "above %d MB as a fixed seeded sample of its pixels)" % (DUMP_MAX_BYTES // 1000000))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: CPU baseline, fixture parity, gather check and per-rank "
+                         "breakdown, frame latency, kernel time, roofline, work counts, 1-GPU projection")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-projection", action="store_true", help="--full without the 1-GPU projection")
     ap.add_argument("--emulate-rank", default=None, metavar="k/N",
                     help="time rank k's share of an N-rank tiled frame on this one GPU")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
@@ -237,6 +277,8 @@ def main():
                          "within 1 %%, rr slightly ahead), else rr")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # CPU test of the rank plumbing
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step, --warmup 0 or more")
     globals()["TILE_ROWS"] = args.tile_rows      # every share / gather of this run
     if args.balance == "lpt" and args.tile_rows % 8:
         ap.error("--balance lpt needs --tile-rows a multiple of 8 (its costs are the 8x8 tiles' ray counts)")
@@ -279,7 +321,7 @@ def main():
         emulate = (k, n)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and emulate is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and emulate is None:
         cpu = cpu_baseline()              # before this process touches the GPU
 
     import numpy as np
@@ -436,11 +478,16 @@ def main():
     parity = None
     if rank == 0 and emulate is None:
         last = df.frame if dist_step else frames[(counter[0] - 1) % F]
-        parity = fixture_parity(last, args.workload)
+        if args.full:
+            parity = fixture_parity(last, args.workload)
+    elif rank == 0:                            # one rank's share: its packed rows
+        last = packed_for[emulate + ((counter[0] - 1) % F,)]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     # ---- the gathered frame equals one whole-frame render, bit for bit (rank 0)
     gather_check = None
-    if dist_step and rank == 0:
+    if args.full and dist_step and rank == 0:
         full = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
         rs[0].render_device(full.data_ptr(), seed=1, stream=stream.cuda_stream)
         torch.cuda.synchronize(dev)
@@ -453,7 +500,7 @@ def main():
     # on the context's streams); the contexts of the frames in flight render one
     # part each (the other frame fills the tails), restored afterwards.
     latency_ms, latency_parts = None, None
-    if world == 1 and emulate is None:
+    if args.full and world == 1 and emulate is None:
         parts_inflight = rs[0].get_option("lv_streams")
         if not any(kv.split("=", 1)[0] == "lv_streams" for kv in args.option):
             rs[0].set_option("lv_streams", parts_default)
@@ -470,19 +517,20 @@ def main():
 
     # ---- the dominant kernel alone: HIP events on its launch stream around
     # every ray-tree kernel launch (rtx_kernel_time), outside the timed region
-    r.set_option("kernel_events", 1)
     kern_ms, kern_launches = [], 0
-    for _ in range(max(3, min(args.steps, 10))):
-        if world == 1 and emulate is None:
-            render_full(0)
-        elif world == 1:
-            share_render(emulate[0], emulate[1], 0)
-        else:
-            pipe.render_share(0, df.bufs[0])
-        ms, kern_launches = r.kernel_time()
-        kern_ms.append(ms)
-    r.set_option("kernel_events", 0)
-    kern_frame_ms = float(np.median(kern_ms))
+    if args.full:
+        r.set_option("kernel_events", 1)
+        for _ in range(max(3, min(args.steps, 10))):
+            if world == 1 and emulate is None:
+                render_full(0)
+            elif world == 1:
+                share_render(emulate[0], emulate[1], 0)
+            else:
+                pipe.render_share(0, df.bufs[0])
+            ms, kern_launches = r.kernel_time()
+            kern_ms.append(ms)
+        r.set_option("kernel_events", 0)
+        kern_frame_ms = float(np.median(kern_ms))
 
     # ---- multi-rank step (C3): what each rank's share and the gather cost, so
     # the driver's N-GPU line explains itself: every rank renders its share
@@ -490,7 +538,7 @@ def main():
     # ranks time the gather itself (events around a blocking dist.gather on the
     # current stream, after a barrier); rank 0 collects them.
     rank_breakdown = None
-    if dist_step:
+    if args.full and dist_step:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         rms_ = []
         for _ in range(3):
@@ -521,7 +569,7 @@ def main():
 
     # ---- 1-GPU projection of the tile-sharded frame (C3) for N = 2, 4, 8
     projection = None
-    if world == 1 and emulate is None and not args.no_projection:
+    if args.full and world == 1 and emulate is None and not args.no_projection:
         def timed(fn, nf):
             """Per-frame ms of nf frames of fn(j) in flight (frame i on context i mod F)."""
             a = time.perf_counter()
@@ -598,18 +646,7 @@ def main():
                 "projected_speedup_no_gather": round(full_ms / lmx, 3)}
 
     if rank == 0:
-        counts = r.count_work(seed=1)           # one counting launch, outside the timed region
-        n_share = emulate[1] if emulate else world
-        px_frame = W * H if n_share == 1 else W * H / n_share
-        ops_frame = roofline.algorithmic_ops(counts) / n_share
-        # whole-frame rates over the timed step (every launch of the frame: level
-        # kernels, resets, re-render, tree reduction), not the level kernels alone
-        step_s = elapsed / args.steps
-        ref_rate_tf = ops_frame / step_s / 1e12
-        wr_gbs = px_frame * roofline.FRAMEBUFFER_BYTES_PER_PX / step_s / 1e9
         value = W * H * args.steps / elapsed / 1e6 if emulate is None else None
-        pm, stale = pmc_profile(args.workload, engine) if (world == 1 and emulate is None) else (None, None)
-        hw = roofline.hw_fp64(pm, kern_frame_ms) if pm else None
         line = {
             "metric": METRIC,
             "value": round(value, 3) if value is not None else None,
@@ -619,10 +656,6 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "frames_in_flight": F,
-            "frame_latency_ms": round(latency_ms, 4) if latency_ms is not None else None,
-            "frame_latency_parts": latency_parts,
-            # SURVEY.md §8(d)'s one-frame-at-a-time rate: W*H / frame_latency_ms
-            "value_single_frame": round(W * H / latency_ms / 1e3, 3) if latency_ms else None,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -633,6 +666,27 @@ def main():
                        "parallelism": "tiles%d-rr x %d ranks, 1 RCCL gather/frame%s"
                        % (TILE_ROWS, world, " (1-rank group, --force-collective)" if world == 1 else "")
                        if dist_step else "1 GPU"},
+        }
+        if emulate:
+            line["emulate_rank"] = {"rank": emulate[0], "nranks": emulate[1],
+                                    "rank_ms_per_frame": round(elapsed / args.steps * 1e3, 4)}
+    if rank == 0 and args.full:
+        counts = r.count_work(seed=1)           # one counting launch, outside the timed region
+        n_share = emulate[1] if emulate else world
+        px_frame = W * H if n_share == 1 else W * H / n_share
+        ops_frame = roofline.algorithmic_ops(counts) / n_share
+        # whole-frame rates over the timed step (every launch of the frame: level
+        # kernels, resets, re-render, tree reduction), not the level kernels alone
+        step_s = elapsed / args.steps
+        ref_rate_tf = ops_frame / step_s / 1e12
+        wr_gbs = px_frame * roofline.FRAMEBUFFER_BYTES_PER_PX / step_s / 1e9
+        pm, stale = pmc_profile(args.workload, engine) if (world == 1 and emulate is None) else (None, None)
+        hw = roofline.hw_fp64(pm, kern_frame_ms) if pm else None
+        line.update({
+            "frame_latency_ms": round(latency_ms, 4) if latency_ms is not None else None,
+            "frame_latency_parts": latency_parts,
+            # SURVEY.md §8(d)'s one-frame-at-a-time rate: W*H / frame_latency_ms
+            "value_single_frame": round(W * H / latency_ms / 1e3, 3) if latency_ms else None,
             "roofline": {
                 "bound": "valu_fp64",
                 "unit": "TFLOP/s",
@@ -673,18 +727,16 @@ def main():
             },
             "cpu_baseline": cpu,
             "work_counts": counts,
-        }
+        })
         if parity is not None:
             line["parity"] = parity
         if gather_check is not None:
             line["gather_check"] = gather_check
         if rank_breakdown is not None:
             line["ranks"] = rank_breakdown
-        if emulate:
-            line["emulate_rank"] = {"rank": emulate[0], "nranks": emulate[1],
-                                    "rank_ms_per_frame": round(elapsed / args.steps * 1e3, 4)}
         if projection:
             line["projection"] = projection
+    if rank == 0:
         print(json.dumps(line), flush=True)
     for rc in rs:
         rc.close()

@@ -8,7 +8,11 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 SCENES = os.path.join(ROOT, "scenes")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"
+# Data of the reference kept as fixtures: its config/world.yml and
+# config/camera.yml as they are, the sha256 of its textures/RubyOnRails.png
+# and the method names of its src/camera.rb.
+REFERENCE = os.path.join(GOLDEN, "reference")
+REFERENCE_TEXTURE_SHA256 = "8c05854821f2ae600d06a73be73feabff5ba22af0fcfb86ff0f9765ecce72429"
 
 
 def pytest_configure(config):

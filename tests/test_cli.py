@@ -72,8 +72,6 @@ def test_cli_loader_matches_python_loader(cli, world, camera):
     assert _cli_dump(cli, w, c) == _py_dump(w, c)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "config", "world.yml")),
-                    reason="reference checkout not present (GPU box)")
 def test_cli_loads_reference_config(cli):
     """The reference's own config/world.yml + camera.yml (duplicate keys, '-' on its
     own line); its missing floor.jpg remapped to our checker, RubyOnRails.png to its

@@ -84,7 +84,7 @@ def test_bench_force_collective_one_rank():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-collective", "--steps", "4",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-collective", "--steps", "4",
                           "--warmup", "1", "--no-cpu-baseline", "--no-projection"],
                          capture_output=True, text=True, timeout=110, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -95,6 +95,31 @@ def test_bench_force_collective_one_rank():
     assert 0.0 < rb["render_ms"][0] < 100.0 and 0.0 <= rb["gather_ms"][0] < 100.0, rb
     assert line["n_gpus"] == 1 and "RCCL" in line["config"]["parallelism"]
     assert line["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_frame(tmp_path):
+    """A plain bench.py run prints the headline line alone (what --full adds is
+    absent) and --dump-outputs writes the last timed C2 frame: float64, the
+    frame's shape, within DESIGN.md §6's tolerance (per-channel RMS <= 1e-4) of
+    the committed oracle fixture columns."""
+    from conftest import GOLDEN
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=110, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["unit"] == "Mpixels/s" and line["higher_is_better"] and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 1920 * 1080 / line["ms_per_step"] / 1e3) < 0.01 * line["value"]
+    for k in ("cpu_baseline", "parity", "roofline", "projection", "work_counts", "frame_latency_ms"):
+        assert k not in line, k
+    assert os.listdir(tmp_path / "dump") == ["frame.npy"]
+    frame = np.load(tmp_path / "dump" / "frame.npy")
+    assert frame.dtype == np.float64 and frame.shape == (1080, 1920, 3)
+    z = np.load(os.path.join(GOLDEN, "c2_full_columns64.npz"))
+    d = frame[:, z["columns"].tolist(), :] - z["frame"]
+    assert (np.sqrt((d ** 2).mean(axis=(0, 1))) <= 1e-4).all()
 
 
 def test_lpt_tile_lists_reassemble_bit_exactly(gpu):
@@ -130,7 +155,7 @@ def test_bench_force_collective_lpt_plan():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-collective", "--balance", "lpt",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-collective", "--balance", "lpt",
                           "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-projection"],
                          capture_output=True, text=True, timeout=110, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

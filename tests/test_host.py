@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, SCENES
+from conftest import REFERENCE, REFERENCE_TEXTURE_SHA256, ROOT, SCENES
 from raytracing_rb_amd import config, png, tiles
 from raytracing_rb_amd._abi import RTX_BOX, RTX_PLANE, RTX_SPHERE
 
@@ -45,9 +45,8 @@ def test_duplicate_keys_last_wins():
     assert list(wall.ambient) == [0.01, 0.01, 0.01]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "config", "world.yml")),
-                    reason="reference checkout not present (GPU box)")
 def test_reference_world_yml_equals_restated_c0():
+    import hashlib
     ref = config.load_yaml(os.path.join(REFERENCE, "config", "world.yml"))
     ours = config.load_yaml(os.path.join(SCENES, "c0_world.yml"))
     for a, b in zip(ref["world_objects"], ours["world_objects"]):
@@ -56,8 +55,8 @@ def test_reference_world_yml_equals_restated_c0():
         assert pa == pb and a["type"] == b["type"]
         if ta == "./textures/RubyOnRails.png":      # the reference's texture, used as-is
             assert tb == ta
-            assert open(os.path.join(REFERENCE, "textures", "RubyOnRails.png"), "rb").read() == \
-                open(os.path.join(SCENES, "textures", "RubyOnRails.png"), "rb").read()
+            with open(os.path.join(SCENES, "textures", "RubyOnRails.png"), "rb") as f:
+                assert hashlib.sha256(f.read()).hexdigest() == REFERENCE_TEXTURE_SHA256
     assert ref["lights"] == ours["lights"]
     assert ref["max_distance"] == ours["max_distance"]
     cam_ref = config.load_yaml(os.path.join(REFERENCE, "config", "camera.yml"))
@@ -389,6 +388,26 @@ def test_bench_launches_its_own_ranks_gloo_stub():
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["stub"] and line["frame_rows_ok"]
+
+
+def test_bench_dump_outputs_whole_frame_or_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size limit is written whole; a larger
+    one as the same seeded sample of its pixels every time, with their indices."""
+    import torch
+    import bench
+    frame = torch.from_numpy(np.random.RandomState(5).rand(20, 30, 3))
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    assert os.listdir(tmp_path / "whole") == ["frame.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "frame.npy"), frame.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    a, ia = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "a" / "frame_index.npy")
+    assert a.dtype == np.float64 and ia.dtype == np.float64 and a.shape == (125, 3) and ia.shape == (125,)
+    assert a.nbytes + ia.nbytes <= 4000 and len(set(ia.tolist())) == 125
+    assert np.array_equal(a, frame.numpy().reshape(600, 3)[ia.astype(np.int64)])
+    assert np.array_equal(ia, np.load(tmp_path / "b" / "frame_index.npy"))
+    assert np.array_equal(a, np.load(tmp_path / "b" / "frame.npy"))
 
 
 def test_bench_refuses_mismatched_world_size():

@@ -64,19 +64,19 @@ print(r.engine())") > $OUT/pmc_json.log 2>&1 && \
   cp $OUT/pmc_$WL.json profiles/pmc_$WL.json
 }
 bench() {
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err && \
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err && \
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o kt --output-format csv -- \
-    python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-projection > $OUT/prof_bench.log 2>&1 && \
+    python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-projection > $OUT/prof_bench.log 2>&1 && \
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_single -o kt --output-format csv -- \
-    python3 bench.py --inflight 1 --option lv_streams=1 --steps 5 --warmup 2 --no-cpu-baseline --no-projection \
+    python3 bench.py --full --inflight 1 --option lv_streams=1 --steps 5 --warmup 2 --no-cpu-baseline --no-projection \
     > $OUT/prof_single.json 2> $OUT/prof_single.err
 }
 bench_c4() {
-  timeout -k 10 600 python bench.py --workload c4 --steps 3 --warmup 1 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+  timeout -k 10 600 python bench.py --full --workload c4 --steps 3 --warmup 1 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
 }
 bench_c4_single() {   # the C4 roofline's kernel time: one frame alone, one context (as prof_single for C2)
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_single_c4 -o kt --output-format csv -- \
-    python3 bench.py --workload c4 --inflight 1 --option lv_streams=1 --steps 2 --warmup 1 --no-cpu-baseline \
+    python3 bench.py --full --workload c4 --inflight 1 --option lv_streams=1 --steps 2 --warmup 1 --no-cpu-baseline \
     --no-projection > $OUT/prof_single_c4.json 2> $OUT/prof_single_c4.err
 }
 
@@ -105,7 +105,7 @@ case $MODE in
   timing) timing "$@" ;;
   stamps) stamps "$@" ;;
   full)  tests && smoke && pmc && bench && bench_c4 ;;
-  quick) tests && timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err ;;
+  quick) tests && timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err ;;
   pmc)   pmc && bench ;;
   pmcbench) if [ "$WL" = c4 ]; then pmc && bench_c4 && bench_c4_single; else pmc && bench; fi ;;
   bench) bench ;;
