@@ -74,6 +74,8 @@ module RTX
   extern 'int rtx_render_multi(void*, int, int, unsigned long long, void*, size_t)'
   extern 'int rtx_render_multi_plan(void*, int, int, void*, int, unsigned long long, void*, size_t)'
   extern 'int rtx_tile_probe(void*, void*, int)'
+  extern 'int rtx_first_hit_device(void*, int, int, int, int, unsigned long long, int, void*, void*, void*)'
+  extern 'int rtx_first_hit(void*, int, int, int, int, unsigned long long, int, void*, void*)'
   extern 'int rtx_lpt_plan(void*, int, int, void*, int, void*)'
   extern 'int rtx_device_count()'
   extern 'int rtx_sync(void*, void*)'

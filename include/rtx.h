@@ -21,6 +21,10 @@
  *   rtx_render_multi      Camera#render_fork + fork_jobs over the node's GPUs with an RCCL gather
  *                                                         src/camera.rb:41-68, src/fork_jobs.rb:1-33
  *   rtx_render_at         Camera#render_at(x, y)         src/camera.rb:70-99
+ *   rtx_first_hit         Camera#lens_func -> World#intersect per pixel  src/camera.rb:129-151, src/world.rb:37-59,
+ *                          with intersect_parameters' n and get_uv + Texture#color of the hit
+ *                                                         src/objects/{sphere,plane,box,texture}.rb
+ *   rtx_first_hit_device  (same, device-resident output, async on a HIP stream)
  *   rtx_trace             RayTracer#trace_sync(x, y, ray) src/ray_tracer.rb:16-46
  *   rtx_path_trace        RayTracer#path_trace_sync(x, y, ray) src/ray_tracer.rb:181-289 (dead code there)
  *   rtx_quantize          Camera#array_to_color + canvas.point  src/camera.rb:105,153-156
@@ -239,6 +243,25 @@ rtx_status rtx_render_multi_plan(rtx_context* const* ctxs, int32_t n, int32_t ti
  * reflective, +3 refractive material; the expensive-tiles-first class of the
  * lanes engine).  Synchronous. */
 rtx_status rtx_tile_probe(rtx_context* ctx, int64_t* out, int32_t n);
+
+/* First-hit feature buffers of pixels [x0,x1) x [y0,y1) for camera sample `sample`
+ * (lens_func(x, y, sample), camera.rb:129-151 -> World#intersect, world.rb:37-59).
+ * d_ids: int32[rows][cols][3], d_geom: double[rows][cols][10], device memory, rows
+ * top-down as rtx_render; either may be NULL.  Async on hip_stream.  Records no raise.
+ * Per pixel, ids = {object (index into world_objects, YAML order), direction (0 :in,
+ * 1 :out, as the object's intersect returns it), data (box face 0..5, else -1)} and
+ * geom = {depth (ray.distance(intersection)), intersection x y z, n.normalize x y z
+ * (intersect_parameters' n; a zero n gives zeros), albedo r g b (diffuse_rate, times
+ * texture.color(*get_uv(intersection)) for a textured sphere or plane; a non-finite
+ * uv gives zeros)}; a miss is {-1, -1, -1} and {max_distance, 0, 0, 0, 0, 0, 0, 0, 0, 0}.
+ * Highlights are not consulted.  RTX_EINVAL for an empty or out-of-frame rectangle,
+ * a sample outside [0, max(pre_sample_times, max_sample_times)), both pointers NULL,
+ * or no scene or camera uploaded. */
+rtx_status rtx_first_hit_device(rtx_context* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                                uint64_t seed, int32_t sample, int32_t* d_ids, double* d_geom, void* hip_stream);
+/* Host-buffer variant, synchronous. */
+rtx_status rtx_first_hit(rtx_context* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                         uint64_t seed, int32_t sample, int32_t* ids, double* geom);
 
 /* Longest-processing-time split of n_tiles tiles (costs[t]) over nranks:
  * tiles by decreasing cost (ties: lower index), each to the rank with the

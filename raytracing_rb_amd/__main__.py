@@ -1,13 +1,30 @@
 """CLI counterpart of src/main.rb:
 
-    python -m raytracing_rb_amd <s|N> <out.png> <world.yml> <camera.yml> [--seed S] [--device D]
+    python -m raytracing_rb_amd <s|N|g> <out.png> <world.yml> <camera.yml> [--seed S] [--device D]
 
 ``s`` renders on one GPU (Camera#render_sync); ``N`` splits the frame over N
-GPU workers (Camera#render_fork).  The reference seeds Random with 1
+GPU workers (Camera#render_fork); ``g`` writes the geometry passes of camera
+sample 0 (normal, depth, albedo) instead.  The reference seeds Random with 1
 (main.rb:10); here the seed keys the counter RNG.
 """
 
 import sys
+
+
+def write_geometry(camera, out_file, max_distance):
+    """Mode ``g``: sample 0's first-hit buffers (Camera.first_hit) as three
+    pictures, quantized like a colour frame: out.normal.png ((n + 1) / 2),
+    out.depth.png (grey, 1 - min(depth / max_distance, 1)), out.albedo.png."""
+    import numpy as np
+    from . import png
+    from .runtime import quantize
+    g = camera.first_hit()
+    stem = out_file[:-4] if out_file.endswith(".png") else out_file
+    depth = 1.0 - np.minimum(g["depth"] / float(max_distance), 1.0)
+    frames = {"normal": (g["normal"] + 1.0) / 2.0, "depth": np.repeat(depth[..., None], 3, axis=2),
+              "albedo": g["albedo"]}
+    for name, fb in frames.items():
+        png.write("%s.%s.png" % (stem, name), quantize(fb))
 
 
 def main(argv=None):
@@ -30,6 +47,8 @@ def main(argv=None):
     camera = Camera(world, camera_file, device=device, seed=seed)
     if mode == "s":
         camera.render_sync(out_file)
+    elif mode == "g":
+        write_geometry(camera, out_file, world.max_distance)
     else:
         camera.render_fork(out_file, int(mode))
     return 0

@@ -102,6 +102,13 @@ class Camera:
         """Float64 framebuffer [H, W, 3], row = y (final image orientation)."""
         return self._r.render(x0, y0, x1, y1, seed=self.seed)
 
+    def first_hit(self, sample=0, x0=0, y0=0, x1=None, y1=None):
+        """The geometry passes next to the colour: lens_func(x, y, sample)
+        (camera.rb:129-151) -> World#intersect (world.rb:37-59) for every pixel.
+        {"object", "direction", "data": int32 [H, W]; "depth": [H, W];
+        "position", "normal", "albedo": [H, W, 3]} (Renderer.first_hit)."""
+        return self._r.first_hit(x0, y0, x1, y1, seed=self.seed, sample=sample)
+
     # -- camera.rb:101-110 + save_image (:36-39)
     def render_sync(self, file_path=None, png_gem_blend=True):
         fb = self.render()

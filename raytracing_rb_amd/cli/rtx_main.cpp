@@ -8,6 +8,14 @@
 //                                             worker): round-robin, or from 8
 //                                             workers cost-balanced lists (LPT over
 //                                             rtx_tile_probe's work map)
+//   rtx g  out.png world.yml camera.yml      geometry passes of camera sample 0
+//                                             (rtx_first_hit: lens_func ->
+//                                             World#intersect, no shading), three
+//                                             files: out.normal.png ((n + 1) / 2),
+//                                             out.depth.png (grey, 1 - min(depth /
+//                                             max_distance, 1)), out.albedo.png;
+//                                             quantized and blended like a colour
+//                                             frame (--no-blend applies)
 // options:
 //   --seed S             RNG seed (main.rb:10 seeds Random with 1; default 1)
 //   --device D           first GPU (default 0)
@@ -170,6 +178,35 @@ std::vector<double> render_fork(const Opts& o, const Scene& sc, const rtx_camera
   return fb;
 }
 
+// rtx g: the three pictures of rtx_first_hit's geom records (10 doubles per
+// pixel), each through array_to_color + canvas.point like a colour frame.
+void write_geometry(const Opts& o, const std::vector<double>& geom, int W, int H, double max_distance) {
+  std::string stem = o.out;
+  if (stem.size() >= 4 && stem.compare(stem.size() - 4, 4, ".png") == 0) stem.resize(stem.size() - 4);
+  const size_t n = (size_t)W * H;
+  std::vector<double> fb(n * 3);
+  std::vector<uint8_t> rgba(n * 4);
+  for (int pass = 0; pass < 3; pass++) {
+    for (size_t i = 0; i < n; i++) {
+      const double* g = geom.data() + i * 10;
+      for (int k = 0; k < 3; k++) {
+        double v;
+        if (pass == 0) {
+          v = (g[4 + k] + 1.0) / 2.0;                            // normal: (n + 1) / 2
+        } else if (pass == 1) {
+          const double d = g[0] / max_distance;                  // depth: 1 - min(depth / max_distance, 1)
+          v = 1.0 - (d < 1.0 ? d : 1.0);
+        } else {
+          v = g[7 + k];                                          // albedo
+        }
+        fb[i * 3 + k] = v;
+      }
+    }
+    if (rtx_quantize(fb.data(), W, H, (size_t)W * 3, o.blend ? 1 : 0, rgba.data()) != RTX_OK) die("quantize failed");
+    png_write_rgba8(stem + (pass == 0 ? ".normal.png" : pass == 1 ? ".depth.png" : ".albedo.png"), rgba.data(), W, H);
+  }
+}
+
 Opts parse_args(int argc, char** argv) {
   Opts o;
   std::vector<std::string> pos;
@@ -248,6 +285,15 @@ int main(int argc, char** argv) {
       return 0;
     }
     const int W = cam.width, H = cam.height;
+    if (o.mode == "g") {                                           // the geometry passes of sample 0
+      rtx_context* c = make_context(o.device, sc, cam);
+      for (const auto& kv : o.opt) check(c, rtx_set_option(c, kv.first.c_str(), kv.second), "option");
+      std::vector<double> geom((size_t)W * H * 10);
+      check(c, rtx_first_hit(c, 0, 0, W, H, o.seed, 0, nullptr, geom.data()), "first_hit");
+      rtx_context_destroy(c);
+      write_geometry(o, geom, W, H, sc.desc.max_distance);
+      return 0;
+    }
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<double> fb;
     int workers = 1;

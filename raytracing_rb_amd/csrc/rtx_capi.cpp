@@ -1580,6 +1580,51 @@ rtx_status rtx_tile_probe(rtx_context* c, int64_t* out, int32_t n) {
   return RTX_OK;
 }
 
+// First-hit feature buffers (rtx_aov.hip).  Like rtx_tile_probe the pass
+// records no raise: the device's raise record and rtx_sync's state stay as
+// they are.
+rtx_status rtx_first_hit_device(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint64_t seed,
+                                int32_t sample, int32_t* d_ids, double* d_geom, void* stream) {
+  if (!c) return RTX_EINVAL;
+  KParams p;
+  rtx_status s = prep(c, p, seed);
+  if (s) return s;
+  if (x0 < 0 || y0 < 0 || x1 > c->cam.width || y1 > c->cam.height || x0 >= x1 || y0 >= y1)
+    return fail(c, RTX_EINVAL, "region [%d,%d)x[%d,%d) empty or outside the %dx%d image", x0, x1, y0, y1,
+                c->cam.width, c->cam.height);
+  const int ms = std::max(c->cam.pre, c->cam.max_samples);
+  if (sample < 0 || sample >= ms) return fail(c, RTX_EINVAL, "sample %d outside [0, %d)", sample, ms);
+  if (!d_ids && !d_geom) return fail(c, RTX_EINVAL, "both output buffers are null");
+  p.x0 = x0;
+  p.nx = x1 - x0;
+  p.y0 = y0;
+  p.nrows = y1 - y0;
+  HIPCHK(c, launch_first_hit(p, sph_mode(c), sample, d_ids, d_geom, (hipStream_t)stream));
+  return RTX_OK;
+}
+
+rtx_status rtx_first_hit(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint64_t seed,
+                         int32_t sample, int32_t* ids, double* geom) {
+  if (!c) return RTX_EINVAL;
+  if (!ids && !geom) return fail(c, RTX_EINVAL, "both output buffers are null");
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  if (x0 < 0 || y0 < 0 || x1 > c->cam.width || y1 > c->cam.height || x0 >= x1 || y0 >= y1)
+    return fail(c, RTX_EINVAL, "region [%d,%d)x[%d,%d) empty or outside the %dx%d image", x0, x1, y0, y1,
+                c->cam.width, c->cam.height);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)(x1 - x0) * (size_t)(y1 - y0);
+  const size_t geom_bytes = geom ? n * 10 * sizeof(double) : 0, ids_bytes = ids ? n * 3 * sizeof(int32_t) : 0;
+  rtx_status s = ensure_scratch(c, geom_bytes + ids_bytes);
+  if (s) return s;
+  double* d_geom = geom ? c->d_scratch : nullptr;
+  int32_t* d_ids = ids ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c->d_scratch) + geom_bytes) : nullptr;
+  if ((s = rtx_first_hit_device(c, x0, y0, x1, y1, seed, sample, d_ids, d_geom, nullptr))) return s;
+  // (stream-ordered blocking copies: no rtx_sync, whose raise record this pass leaves alone)
+  if (geom) HIPCHK(c, hipMemcpy(geom, d_geom, geom_bytes, hipMemcpyDeviceToHost));
+  if (ids) HIPCHK(c, hipMemcpy(ids, d_ids, ids_bytes, hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+
 rtx_status rtx_lpt_plan(const int64_t* costs, int32_t n_tiles, int32_t nranks, int32_t* plan, int32_t cap,
                         int32_t* per_rank) {
   if (n_tiles < 0 || nranks < 1 || (n_tiles > 0 && !costs) || !per_rank) return RTX_EINVAL;

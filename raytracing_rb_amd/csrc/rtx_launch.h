@@ -218,5 +218,10 @@ hipError_t launch_unpack(const double* gathered, int w, int h, int tile_rows, in
 hipError_t launch_unpack_plan(const double* gathered, int w, int h, int tile_rows, int n, int per_rank,
                               const int32_t* d_plan, double* out, size_t stride, hipStream_t s);
 hipError_t launch_tile_probe(KParams p, int32_t* cls, hipStream_t s);
+// First-hit feature buffers of the region of `p` for camera sample `sample`
+// (rtx_aov.hip): d_ids int32[nrows][nx][3], d_geom double[nrows][nx][10];
+// either may be null.  mode: SphMode (a hierarchy mode walks the hierarchy,
+// staged in LDS when it fits, else from global memory).
+hipError_t launch_first_hit(KParams p, int mode, int32_t sample, int32_t* d_ids, double* d_geom, hipStream_t s);
 
 }  // namespace rtx

@@ -104,6 +104,22 @@ class Renderer:
         self._check(self.lib.rtx_path_trace(self.h, len(rays), _dp(rays), _dp(out)))
         return out
 
+    def first_hit(self, x0=0, y0=0, x1=None, y1=None, seed=1, sample=0):
+        """First-hit feature buffers of camera sample ``sample`` (rtx_first_hit):
+        lens_func(x, y, sample) -> World#intersect per pixel, no shading.  A dict of
+        arrays over the region [H, W] (row = y, top first): ``object`` (index into
+        world_objects, -1 = miss), ``direction`` (0 :in, 1 :out), ``data`` (box face
+        or -1), int32; ``depth`` [H, W] (max_distance on a miss); ``position``,
+        ``normal`` (normalized), ``albedo`` [H, W, 3], float64."""
+        x1 = self.width if x1 is None else x1
+        y1 = self.height if y1 is None else y1
+        h, w = max(y1 - y0, 0), max(x1 - x0, 0)
+        ids = np.empty((h, w, 3), np.int32)
+        geom = np.empty((h, w, 10), np.float64)
+        self._check(self.lib.rtx_first_hit(self.h, x0, y0, x1, y1, seed, sample,
+                                           ids.ctypes.data_as(C.POINTER(C.c_int32)), _dp(geom)))
+        return split_first_hit(ids, geom)
+
     def count_work(self, seed=1):
         cnt = (C.c_uint64 * RTX_NCOUNT)()
         self._check(self.lib.rtx_count_work(self.h, seed, cnt))
@@ -116,6 +132,14 @@ class Renderer:
         row_stride = (x1 - x0) * 3 if row_stride is None else row_stride
         self._check(self.lib.rtx_render_device(self.h, x0, y0, x1, y1, seed, C.c_void_p(d_out), row_stride,
                                                C.c_void_p(stream or 0)))
+
+    def first_hit_device(self, d_ids, d_geom, seed=1, sample=0, x0=0, y0=0, x1=None, y1=None, stream=None):
+        """rtx_first_hit_device: d_ids int32 [rows, cols, 3], d_geom float64 [rows, cols, 10]
+        (device pointers; either may be None).  Records no raise."""
+        x1 = self.width if x1 is None else x1
+        y1 = self.height if y1 is None else y1
+        self._check(self.lib.rtx_first_hit_device(self.h, x0, y0, x1, y1, seed, sample, C.c_void_p(d_ids or 0),
+                                                  C.c_void_p(d_geom or 0), C.c_void_p(stream or 0)))
 
     def rows_per_rank(self, tile_rows, nranks):
         return self.lib.rtx_tiles_rows_per_rank(self.height, tile_rows, nranks)
@@ -187,6 +211,12 @@ class Renderer:
                                           C.c_void_p(stream or 0))
         if st:
             raise RtxError(st, "rtx_quantize_device failed")
+
+
+def split_first_hit(ids, geom):
+    """The named views of rtx_first_hit's buffers: ids [H, W, 3], geom [H, W, 10]."""
+    return {"object": ids[..., 0], "direction": ids[..., 1], "data": ids[..., 2], "depth": geom[..., 0],
+            "position": geom[..., 1:4], "normal": geom[..., 4:7], "albedo": geom[..., 7:10]}
 
 
 def render_multi(renderers, tile_rows=8, seed=1):
