@@ -371,6 +371,11 @@ rtx_status rtx_get_option(rtx_context* ctx, const char* key, int64_t* value);
          launch per level, 1 three launches per level over dense queues: trace, shadow, shade; same bits; used up
          to 16 lights), "lv_static" (bounce levels: % of a level launch's 64-ray chunks scheduled statically, the
          rest claimed from sharded counters; -1 [default] = 100 up to 512 spheres, else 50; same bits),
+         "lv_round" (bounce levels: who owns the static chunks: 0 a wave, wave w of the launch's W waves takes
+         chunks w, w + W, ...; R in 1..4096 a workgroup, b of G, which owns the chunks k G R + b R + r, r < R, of
+         every round k and whose waves take them in order from a counter in LDS whenever they are free, so no wave
+         idles while its workgroup's slowest holds the CU; a launch whose LDS has no room for the counter keeps 0;
+         -1 [default] = 8 up to 512 spheres, else 32; same bits),
          "lv_compact" (bounce levels: 1 park the rays that hit something in a per-wave LDS ring and run the
          shadow walks and shading on full waves, 0 off, -1 [default] = on whenever the rings fit the walk's
          LDS; a hierarchy too large for the full ring next to it gets the compact ring (hit point and ids only,

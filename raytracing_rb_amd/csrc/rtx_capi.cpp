@@ -83,6 +83,7 @@ struct rtx_context {
   int64_t opt_lv_floor = 1 << 20;    // bounce levels: at least this many staging and 4x this many tree records
   int64_t opt_lv_split = 0;          // bounce levels: 1 = three phase launches per level (trace / shadow / shade)
   int64_t opt_lv_static = -1;        // bounce levels: % of a launch's chunks scheduled statically (-1 auto)
+  int64_t opt_lv_round = -1;         // bounce levels: static chunks in rounds of R per workgroup (0 per wave, -1 auto)
   int64_t opt_lv_compact = -1;       // bounce levels: 1 = park hits in an LDS ring and shade full waves, -1 auto (when it fits)
   int64_t opt_lv_grid_div = 1;       // bounce levels: persistent level grids = resident workgroups / this
   int64_t opt_lv_fin_grid = 0;       // bounce levels: tree reduction blocks per CU (grid-stride over tiles), 0 = one block per tile
@@ -276,7 +277,8 @@ rtx_status rtx_get_option(rtx_context* c, const char* key, int64_t* value) {
       {"lds_stack", c->opt_lds_stack}, {"tile_order", c->opt_tile_order},   {"sphere_src", c->opt_sphere_src},
       {"kernel_events", c->opt_kernel_events}, {"lv_batch", c->opt_lv_batch},
       {"lv_stage_pct", c->opt_lv_stage_pct}, {"lv_rec_pct", c->opt_lv_rec_pct}, {"lv_floor", c->opt_lv_floor},
-      {"lv_split", c->opt_lv_split}, {"lv_static", c->opt_lv_static}, {"lv_compact", c->opt_lv_compact},
+      {"lv_split", c->opt_lv_split}, {"lv_static", c->opt_lv_static}, {"lv_round", c->opt_lv_round},
+      {"lv_compact", c->opt_lv_compact},
       {"lv_streams", c->opt_lv_streams}, {"lv_grid_div", c->opt_lv_grid_div},
       {"lv_redo_blocks", c->opt_lv_redo_blocks},
       {"lv_fin_grid", c->opt_lv_fin_grid}, {"lv_ray_bytes", c->opt_lv_ray_bytes},
@@ -354,6 +356,11 @@ rtx_status rtx_set_option(rtx_context* c, const char* key, int64_t value) {
   if (!strcmp(key, "lv_static")) {         // bounce levels: % of chunks scheduled statically, -1 auto
     if (value < -1 || value > 100) return fail(c, RTX_EINVAL, "lv_static must be in [-1, 100]");
     c->opt_lv_static = value;
+    return RTX_OK;
+  }
+  if (!strcmp(key, "lv_round")) {          // bounce levels: static chunks in rounds of R per workgroup, 0 per wave, -1 auto
+    if (value < -1 || value > LV_ROUND_MAX) return fail(c, RTX_EINVAL, "lv_round must be in [-1, %d]", LV_ROUND_MAX);
+    c->opt_lv_round = value;
     return RTX_OK;
   }
   if (!strcmp(key, "lv_grid_div")) {       // bounce levels: level grids = resident workgroups / this
@@ -1036,6 +1043,12 @@ static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_
   // workgroup's LDS with room to spare (C2: 5.35 vs 5.9 ms at 50 %), half
   // static for large hierarchies (C4: 437 vs 518 ms all static).
   p.lv_static_pct = c->opt_lv_static >= 0 ? (int32_t)c->opt_lv_static : (c->scene.n_sphere <= 512 ? 100 : 50);
+  // The static chunks' owner: a wave (0), or a workgroup whose waves claim them in rounds of R from a
+  // counter in LDS.  Auto: R = 8 up to 512 spheres (C2 bench 461.3 -> 497.5 Mpix/s, the
+  // 1/8 share 0.703 -> 0.677 ms; 32 ties on the frame and loses on the share, 128 and 512 lose),
+  // 32 above (C4 31.53 -> 31.95 Mpix/s; 8: 31.72).
+  p.lv_round = c->opt_lv_round >= 0 ? (int32_t)c->opt_lv_round : (c->scene.n_sphere <= 512 ? 8 : 32);
+  p.lds_sched = -1;
   p.extra_count = (int32_t*)(buf + parts * set);
   p.extra_list = p.extra_count + 64;
   p.lv_scap = (uint32_t)scap;

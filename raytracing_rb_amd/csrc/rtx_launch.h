@@ -26,6 +26,9 @@ constexpr int LV_CLAIMS = 16;                   // sharded chunk-claim counters 
 constexpr int LV_DONE = 16;                     // wave-completion counters per level launch (lv_level_done)
 constexpr int LV_CELL_BITS_MAX = 4;             // ray bins (option lv_sort): origin cells per axis = 2^lv_cell_bits
 constexpr int LV_BINS = 8 << (3 * LV_CELL_BITS_MAX); // x 8 direction octants: at most 32,768 bins
+}  // namespace rtx
+#include "rtx_sched.h"                          // LV_ROUND_MAX, lv_static_chunks, lv_round_chunk (host and device)
+namespace rtx {
 struct LevelCtl {
   uint32_t count0;                              // level-0 items of the batch
   uint32_t redo_n;                              // level-0 items handed to the lanes engine (capacity overflow)
@@ -103,6 +106,10 @@ struct KParams {
   unsigned long long* lv_acc;      // per call: {redo_n, dropped, count[0..LV_MAXL]} summed over batches (or null)
   int32_t lv_split;                // 1: three phase launches per level (k_lv_trace / k_lv_shadow / k_lv_shade)
   int32_t lv_static_pct;           // % of a level launch's chunks scheduled statically (the rest: sharded claims)
+  int32_t lv_round;                // static chunks: 0 wave w takes w, w + W, ...; R > 0 rounds of R chunks per workgroup,
+                                   // claimed from the LDS word at lds_sched (option lv_round; the launcher clears it
+                                   // where that word finds no room)
+  int32_t lds_sched;               // LDS byte offset of the workgroup's claim counter (lv_round > 0)
   double* lv_hit;                  // split: hit queue, LV_HIT_BYTES per hit, LV_SLICES << lv_hslice_log2 slots
   double* lv_area;                 // split: {1 - covers, raise} per (hit, light)
   int32_t lv_compact;              // k_level: park hits in an LDS ring, shade full waves (-1 auto, 0 off, 1 on, 2 compact ring)

@@ -63,6 +63,55 @@ static_assert(RAY_DOUBLES * 8 == (int)RAY_BYTES && HIT_DOUBLES * 8 == (int)LV_HI
 // summed into row 7): 6 phases, chunks, lanes with a hit.
 static __device__ unsigned long long rtx_stamps_lv[8 * 8];
 
+// Diagnostic builds: how evenly a level launch's chunks fall on its waves
+// (DESIGN.md §3.7), in ticks of the 100 MHz wall() clock, per tree level
+// (levels >= 7 in row 7): [0] sum over waves of (wave end - wave start),
+// [1] sum over workgroups of waves x (last wave end - first wave start),
+// [2] first wave start and [3] last wave end of the launch, [4] sum over
+// workgroups of (last wave end - first wave start), [5] workgroups, [6] waves.
+// 1 - [0] / [1] is the share of the workgroups' SIMD time in which a wave had
+// left while its workgroup still held the CU; ([3] - [2]) - [4] / [5] is the
+// launch's tail.  Read and reset by rtxdbg_read_wg_stamps ([2]: reset to ~0).
+static __device__ unsigned long long rtx_stamps_wg[8 * 8];
+
+#if RTX_STAMPS
+static __shared__ unsigned long long lv_wg[3];   // the workgroup's first wave start, last wave end, waves that ended
+#endif
+struct LvWgStamps {
+  unsigned long long w0 = 0;
+  // a wave's start (all waves of the workgroup get here: a barrier of its own)
+  __device__ __forceinline__ void begin() {
+#if RTX_STAMPS
+    if (threadIdx.x == 0) {
+      lv_wg[0] = ~0ull;
+      lv_wg[1] = 0ull;
+      lv_wg[2] = 0ull;
+    }
+    __syncthreads();
+    w0 = wall();
+    if (__lane_id() == 0) atomicMin(&lv_wg[0], w0);
+#endif
+  }
+  // a wave's end: no barrier; the workgroup's last wave to get here adds the workgroup's span
+  __device__ __forceinline__ void end(int level) {
+#if RTX_STAMPS
+    if (__lane_id() != 0) return;
+    const unsigned long long w1 = wall(), waves = blockDim.x >> 6;
+    unsigned long long* g = rtx_stamps_wg + 8 * (level < 7 ? level : 7);
+    atomicAdd(&g[0], w1 - w0);
+    atomicAdd(&g[6], 1ull);
+    atomicMax(&lv_wg[1], w1);
+    if (atomicAdd(&lv_wg[2], 1ull) != waves - 1) return;
+    const unsigned long long first = atomicMin(&lv_wg[0], ~0ull), last = atomicMax(&lv_wg[1], 0ull);   // (LDS reads)
+    atomicAdd(&g[1], waves * (last - first));
+    atomicMin(&g[2], first);
+    atomicMax(&g[3], last);
+    atomicAdd(&g[4], last - first);
+    atomicAdd(&g[5], 1ull);
+#endif
+  }
+};
+
 int levels_rec_bytes(int n_light) {
   const int nl = n_light > 1 ? n_light : 1;
   return (8 + 24 * nl + 15) & ~15;       // {meta, first child} + one leaf per fired light
@@ -323,12 +372,32 @@ __device__ __forceinline__ void lv_level_done(const KParams& p, int e) {
 }
 
 // Chunk schedule of a launch: the first p.lv_static_pct % of the chunks
-// static (wave w of the grid's W waves takes chunks w, w + W, ...: no
-// atomics, but imbalanced when ray costs vary a lot, C4), the rest dynamic
-// over LV_CLAIMS sharded counters, counter j handing out chunks
-// S + j, S + j + LV_CLAIMS, ...; a wave starts at its home counter (wave id
-// mod LV_CLAIMS) and, once that is exhausted, reads all counters (one load
-// per lane, no atomic) and moves to one that is not.
+// static, the rest dynamic.  The static chunks (no device atomics, but
+// imbalanced when ray costs vary a lot, C4) belong to a wave (p.lv_round = 0:
+// wave w of the grid's W waves takes chunks w, w + W, ...) or to a workgroup
+// (p.lv_round = R > 0, lv_round_chunk: rounds of R chunks per workgroup, its
+// waves take the next one from one LDS counter, lane 0's atomicAdd, whenever
+// they are free: a wave that drew cheap chunks takes more of them, and none
+// idles on its SIMD while the workgroup's slowest still holds the CU's LDS
+// and registers).  The dynamic chunks go over LV_CLAIMS sharded counters,
+// counter j handing out chunks S + j, S + j + LV_CLAIMS, ...; a wave starts
+// at its home counter (wave id mod LV_CLAIMS) and, once that is exhausted,
+// reads all counters (one load per lane, no atomic) and moves to one that is
+// not.  Everything here is wave-uniform (scalar registers), and the rounds
+// add no state to it: the round size and the counter's place are read from
+// the kernel arguments at each claim, the workgroup and the grid from the
+// dispatch, and `next` = ~0 says that the workgroup's static part is over
+// (the level kernels sit at the register limit).
+//
+// The LDS counter: lv_sched_init before the workgroup's first barrier; waves
+// leave one by one once their claims fail (no barrier after the loop).
+__device__ __forceinline__ uint32_t* lv_sched_word(const KParams& p) {
+  extern __shared__ float4 lds_sph[];
+  return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_sph) + p.lds_sched);
+}
+__device__ __forceinline__ void lv_sched_init(const KParams& p) {
+  if (p.lv_round > 0 && threadIdx.x == 0) *lv_sched_word(p) = 0u;
+}
 struct LvSched {
   uint32_t* ctrs;              // this launch's claim counters (ctrs[j * 32])
   uint32_t next, step, j, pct;
@@ -338,8 +407,16 @@ struct LvSched {
     j = next & (LV_CLAIMS - 1);
   }
   __device__ __forceinline__ int wave_id() const { return (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); }
-  __device__ __forceinline__ bool claim(uint32_t chunks, uint32_t& c) {
-    const uint32_t S = (uint32_t)(((uint64_t)chunks * pct) / 100);
+  __device__ __forceinline__ bool claim(const KParams& p, uint32_t chunks, uint32_t& c) {
+    const uint32_t S = lv_static_chunks(chunks, pct);
+    if (p.lv_round > 0 && next != ~0u) {
+      uint32_t n = 0;
+      if (__lane_id() == 0) n = atomicAdd(lv_sched_word(p), 1u);
+      n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
+      c = lv_round_chunk(n, blockIdx.x, gridDim.x, (uint32_t)p.lv_round);
+      if (c < S) return true;
+      next = ~0u;                // the workgroup's static part is exhausted (c increases with n): never again
+    }
     if (next < S) {
       c = next;
       next += step;
@@ -419,6 +496,8 @@ __device__ __forceinline__ void lv_stage_scene(const KParams& p, float4* lds_sph
       }
     }
     __syncthreads();
+  } else if (p.lv_round > 0) {
+    __syncthreads();                          // (uniform) nothing staged: lv_sched_init's counter before any claim
   }
 }
 
@@ -707,6 +786,9 @@ __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
   LvQueue in;
   lv_in_queue(p, level, in);
   if (in.chunks == 0) return;                 // uniform: before any barrier
+  LvWgStamps wgs;                             // RTX_STAMPS diagnostic build only
+  wgs.begin();
+  lv_sched_init(p);
   lv_stage_scene<SPH, BS>(p, lds_sph);
   const uint32_t base = lv_base(p, level);
   const int depth = p.cam->depth - level;
@@ -723,7 +805,7 @@ __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
   }
   uint32_t chunk;
   const uint32_t nch = lv_chunks(p, in, level);
-  while (sched.claim(nch, chunk)) {
+  while (sched.claim(p, nch, chunk)) {
     if (RTX_STAMPS) {
       t0 = stamp();
       nchunks++;
@@ -819,6 +901,7 @@ __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
     RTX_LV_STAMP(5)
   }
 #undef RTX_LV_STAMP
+  wgs.end(level);
   if (RTX_STAMPS && __lane_id() == 0) {
     for (int k = 0; k < 6; k++) atomicAdd(&rtx_stamps[k], tS[k]);
     atomicAdd(&rtx_stamps[6], nchunks);
@@ -879,6 +962,9 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
   LvQueue in;
   lv_in_queue(p, level, in);
   if (in.chunks == 0) return;                 // uniform: before any barrier
+  LvWgStamps wgs;                             // RTX_STAMPS diagnostic build only
+  wgs.begin();
+  lv_sched_init(p);
   lv_stage_scene<SPH, BS>(p, lds_sph);
   const uint32_t base = lv_base(p, level);
   const int depth = LAST ? 1 : p.cam->depth - level;   // LAST: the batch's last level, compiled apart
@@ -901,7 +987,7 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
   while (true) {
     {                                         // first half, chunk by chunk, until 64 hits are parked
       uint32_t chunk = 0;
-      if (got) got = sched.claim(nch, chunk);   // (never again once exhausted)
+      if (got) got = sched.claim(p, nch, chunk);   // (never again once exhausted)
       if (RTX_STAMPS) t0 = stamp();
       if (got) {
         if (RTX_STAMPS) nchunks++;
@@ -1096,6 +1182,7 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
     RTX_LV_STAMP(5)
   }
 #undef RTX_LV_STAMP
+  wgs.end(level);
   if (RTX_STAMPS && __lane_id() == 0) {
     for (int k = 0; k < 6; k++) atomicAdd(&rtx_stamps[k], tS[k]);
     atomicAdd(&rtx_stamps[6], nchunks);
@@ -1148,6 +1235,7 @@ __global__ __launch_bounds__(BS, RTX_LV_WALK_WPS) void k_lv_trace(KParams p, int
   LvQueue in;
   lv_in_queue(p, level, in);
   if (in.chunks == 0) return;                 // uniform: before any barrier
+  lv_sched_init(p);
   lv_stage_scene<SPH, BS>(p, lds_sph);
   const uint32_t base = lv_base(p, level);
   const int depth = p.cam->depth - level;
@@ -1155,7 +1243,7 @@ __global__ __launch_bounds__(BS, RTX_LV_WALK_WPS) void k_lv_trace(KParams p, int
   const int slice = sched.wave_id() & (LV_SLICES - 1);
   const uint32_t hlog2 = (uint32_t)p.lv_hslice_log2, hcap = 1u << hlog2;
   uint32_t chunk;
-  while (sched.claim(in.chunks, chunk)) {
+  while (sched.claim(p, in.chunks, chunk)) {
     uint32_t s, off, i;
     bool active = in.item(chunk, s, off, i);
     const uint32_t slot = level == 0 ? i : (s << p.lv_slice_log2) + off;
@@ -1230,10 +1318,11 @@ __global__ __launch_bounds__(BS, RTX_LV_WALK_WPS) void k_lv_shadow(KParams p, in
   LvQueue in;
   in.sliced(p.lv_ctl->sh[level], 1u << hlog2, nL);
   if (in.chunks == 0) return;
+  lv_sched_init(p);
   lv_stage_scene<SPH, BS>(p, lds_sph);
   LvSched sched(p.lv_ctl->claim[1][level], p.lv_static_pct);
   uint32_t chunk;
-  while (sched.claim(in.chunks, chunk)) {
+  while (sched.claim(p, in.chunks, chunk)) {
     uint32_t s, off, t;
     if (in.item(chunk, s, off, t)) {          // (lanes past their slice idle until the next chunk)
       const uint32_t hs = (s << hlog2) + off / nL, li = off % nL;   // hit slot, light
@@ -1260,13 +1349,15 @@ __device__ __forceinline__ void k_lv_shade_body(const KParams& p, int level) {
   const uint32_t hlog2 = (uint32_t)p.lv_hslice_log2;
   LvQueue in;
   in.sliced(p.lv_ctl->sh[level], 1u << hlog2, 1u);
-  if (in.chunks == 0) return;
+  if (in.chunks == 0) return;                 // uniform: before the barrier
+  lv_sched_init(p);
+  if (p.lv_round > 0) __syncthreads();        // (uniform) the claim counter is set before any wave claims
   const uint32_t base = lv_base(p, level);
   const int nL = S.n_light;
   LvSched sched(p.lv_ctl->claim[2][level], p.lv_static_pct);
   const int slice = sched.wave_id() & (LV_SLICES - 1);
   uint32_t chunk;
-  while (sched.claim(in.chunks, chunk)) {
+  while (sched.claim(p, in.chunks, chunk)) {
     uint32_t s, off, t;
     const bool shade = in.item(chunk, s, off, t);
     const uint32_t hs = (s << hlog2) + off;   // hit slot
@@ -1859,6 +1950,16 @@ extern "C" int rtxdbg_read_walkstats(unsigned long long* out, int reset) {   // 
   return 0;
 }
 
+extern "C" int rtxdbg_read_wg_stamps(unsigned long long* out, int reset) {   // diagnostic builds: [8 levels][8]
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rtx_stamps_wg), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long z[64] = {};
+    for (int d = 0; d < 8; d++) z[8 * d + 2] = ~0ull;   // (the launch's first wave start: a minimum)
+    if (hipMemcpyToSymbol(HIP_SYMBOL(rtx_stamps_wg), z, sizeof z) != hipSuccess) return -1;
+  }
+  return 0;
+}
+
 extern "C" int rtxdbg_read_level_stamps(unsigned long long* out, int reset) {   // diagnostic builds: [8 levels][8]
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rtx_stamps_lv), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
   if (reset) {
@@ -1975,6 +2076,18 @@ static hipError_t launch_level_bs(const KParams& p, int kind, int level, long ca
       kern = k_level<SPH, BS, XR_WALK>;
     }
   }
+  // rounds (lv_round): the workgroup's claim counter after everything else; where the layout leaves no
+  // room for it, this launch keeps the per-wave static schedule (placed whatever lv_round is: a kernel's
+  // dynamic LDS size, which launch_fit caches and raises the kernel's limit to, does not depend on the option)
+  {
+    const size_t at = (lds + 3) & ~(size_t)3;
+    if (at + 4 <= (sph_is_bvh(SPH) ? LDS_TOTAL_BYTES : LDS_LIN_BLOCK_BYTES)) {
+      q.lds_sched = (int32_t)at;
+      lds = at + 4;
+    } else {
+      q.lv_round = 0;
+    }
+  }
   int cus = 0, per_cu = 0;                     // (also raises the kernel's dynamic-LDS limit once)
   const hipError_t e = cus_and_fit(reinterpret_cast<const void*>(kern), BS, lds, cus, per_cu);
   if (e != hipSuccess) return e;
@@ -2015,11 +2128,14 @@ static hipError_t launch_level_mode(const KParams& p, int mode, int kind, int le
 }
 
 static hipError_t launch_shade(const KParams& p, int level, long cap_items, hipStream_t s, KernelEvents* kev) {
+  KParams q = p;
+  q.lds_sched = 0;                             // its only LDS: the workgroup's claim counter (lv_round)
+  const size_t lds = q.lv_round > 0 ? 16 : 0;
   int cus = 0, per_cu = 0;
-  const hipError_t e = cus_and_fit(reinterpret_cast<const void*>(k_lv_shade), BS_SHADE, 0, cus, per_cu);
+  const hipError_t e = cus_and_fit(reinterpret_cast<const void*>(k_lv_shade), BS_SHADE, lds, cus, per_cu);
   if (e != hipSuccess) return e;
   return launch_timed(k_lv_shade, std::min<long>((cap_items + BS_SHADE - 1) / BS_SHADE, (long)cus * per_cu), BS_SHADE,
-                      0, s, kev, p, level);
+                      lds, s, kev, q, level);
 }
 
 // A level's binning (option lv_sort): count, prefix, scatter; grids sized for
