@@ -169,3 +169,144 @@ def test_fuzz_scenes_python_and_c_restatements_agree(oracle_lib, tmp_path, seed)
                 pst[y, x] = codes[e.kind]
     assert np.array_equal(st, pst)
     assert np.array_equal(py[st == 0].view(np.uint64), fb[st == 0].view(np.uint64))
+
+
+# ---------------------------------------------------------------- posed scenes
+# sha256 (first 16 hex digits) of fuzz_scenes.make(seed, dir, 48, 27)'s world + camera
+# text for seeds 0-23, the textures directory written as "<textures>", taken from the
+# generator before pose() was added: the 24 fuzz scenes are fixtures and stay as they are.
+MAKE_SHA = (
+    "133e001976256920", "3587bc20a33507f4", "665bc78d1a863f46", "1ddfd868aedb1eb7",
+    "40e47be50243f2d8", "a4141fbeb26a1d4f", "10062a99d4ad150b", "332ee6504d5f532e",
+    "2b8007e531187beb", "0a181ca613d24926", "612177f054f3e9bd", "0496e02b18ec5037",
+    "2f5a57badddd3372", "75cf10a3e06de563", "a10ea7f0486c1fdb", "fd3c85469fc261e1",
+    "cb94387ce413899d", "a95dbdea57ec0bf3", "1a644837f875c496", "8152b872179c1bb7",
+    "bdd8988c29d5a997", "d9443c053c72e155", "9353dd2f8e04217a", "32e2c6ece51143c9",
+)
+
+
+def test_fuzz_scene_files_unchanged(tmp_path):
+    import fuzz_scenes
+    for seed, sha in enumerate(MAKE_SHA):
+        h = hashlib.sha256()
+        for p in fuzz_scenes.make(seed, tmp_path, 48, 27):
+            with open(p) as f:
+                h.update(f.read().replace(fuzz_scenes.TEXTURES, "<textures>").encode())
+        assert h.hexdigest()[:16] == sha, seed
+
+
+def test_posed_seeds_cover_every_combination():
+    import fuzz_scenes
+    seeds = fuzz_scenes.POSED_SEEDS
+    assert len(seeds) == 12 and [s % 12 for s in seeds] == list(range(12))
+    params = [fuzz_scenes.posed_parameters(s) for s in seeds]
+    assert {(sc, off / sc) for sc, off, _ in params} == {(sc, off) for sc in fuzz_scenes.POSED_SCALES
+                                                         for off in fuzz_scenes.POSED_OFFSETS}
+    assert [b for _, _, b in params] == [(k // 2) % 2 == 1 for k in range(12)]
+
+
+def test_pose_maps_points_directions_and_lengths(tmp_path):
+    """pose() on mix_world.yml: every point is t + scale Q p with one orthonormal Q
+    and one t, directions keep their angles and take lengths in [0.4, 2.5], lengths
+    scale, the camera's up is neither unit nor perpendicular, intrinsics stay."""
+    import fuzz_scenes
+    src = (os.path.join(SCENES, "mix_world.yml"), os.path.join(SCENES, "mix_camera.yml"))
+    scale = 40.0
+    w, c = fuzz_scenes.pose(src[0], src[1], tmp_path, 5, scale, 2000.0, True)
+    a, b = config.load_yaml(src[0]), config.load_yaml(w)
+    ca, cb = config.load_yaml(src[1]), config.load_yaml(c)
+    assert b["max_distance"] == 9.0 * scale
+    pts, dirs = [], []
+    for ia, ib in zip(a["lights"] + a["world_objects"], b["lights"] + b["world_objects"]):
+        pa, pb = ia["properties"], ib["properties"]
+        assert list(pa) == list(pb)
+        for k in pa:
+            if k in fuzz_scenes.POINT_KEYS:
+                pts.append((pa[k], pb[k]))
+            elif k in fuzz_scenes.DIRECTION_KEYS:
+                dirs.append((pa[k], pb[k]))
+            elif k in fuzz_scenes.LENGTH_KEYS:
+                assert pb[k] == pa[k] * scale, k
+            elif k == "texture_file_path":
+                assert os.path.isabs(pb[k]) and os.path.exists(pb[k])
+            else:
+                assert pb[k] == pa[k], k
+    pts.append((ca["position"], cb["position"]))
+    dirs.append((ca["front"], cb["front"]))
+    P, P2 = np.array([p for p, _ in pts]), np.array([p for _, p in pts])
+    D, D2 = np.array([d for d, _ in dirs]), np.array([d for _, d in dirs])
+    t = P2[-1]                                                    # the camera was at the origin
+    assert np.abs(t).max() <= 2000.0 and np.abs(t).max() > 1.0
+    Q = np.linalg.lstsq(P * scale, P2 - t, rcond=None)[0].T
+    assert np.allclose(Q.dot(Q.T), np.eye(3), atol=1e-9) and np.linalg.det(Q) > 0
+    ln = np.linalg.norm(D2, axis=1) / np.linalg.norm(D, axis=1)
+    assert (ln >= 0.4).all() and (ln <= 2.5).all() and len(set(ln.round(9))) == len(ln)
+    assert np.allclose(D2 / np.linalg.norm(D2, axis=1)[:, None], (D / np.linalg.norm(D, axis=1)[:, None]).dot(Q.T),
+                       atol=1e-9)
+    up, front = np.array(cb["up"]), np.array(cb["front"])
+    cos = up.dot(front) / np.linalg.norm(up) / np.linalg.norm(front)
+    assert abs(cos - 0.3 / np.sqrt(1.09)) < 1e-9
+    for k in ca:
+        if k not in ("position", "up", "front"):
+            assert cb[k] == ca[k], k
+
+
+@pytest.mark.parametrize("k", range(12))
+def test_posed_scenes_python_and_c_restatements_agree(oracle_lib, tmp_path, k):
+    """make_posed (a random rotation, scale 0.02 / 1 / 40, offset up to 1e5 scale,
+    non-unit and non-perpendicular bases, max_distance inside the geometry on half
+    of them): the two restatements agree bit for bit off the origin pose, raise
+    sites included."""
+    import fuzz_scenes
+    from oracle.rb_vec3 import RtxError
+    seed = fuzz_scenes.POSED_SEEDS[k]
+    w, c = fuzz_scenes.make_posed(seed, tmp_path, 12, 8)
+    sd, cd = config.load_scene(w, c)
+    fb, st, rc = Oracle(sd, cd).render(seed=seed)
+    _, cam = rt_ref.load_scene(w, c, seed=seed)
+    codes = {"zero_vec": 1, "color_gt1": 2, "domain": 3}
+    py = np.zeros_like(fb)
+    pst = np.zeros_like(st)
+    for x in range(cd.width):
+        for y in range(cd.height):
+            try:
+                py[y, x] = cam.render_at(x, y).to_a()
+            except RtxError as e:
+                pst[y, x] = codes[e.kind]
+    assert np.array_equal(st, pst)
+    assert np.array_equal(py[st == 0].view(np.uint64), fb[st == 0].view(np.uint64))
+
+
+def _distinct_from_mode(fb):
+    _, counts = np.unique(np.ascontiguousarray(fb).reshape(-1, 3), axis=0, return_counts=True)
+    return 1.0 - counts.max() / float(counts.sum())
+
+
+@pytest.mark.parametrize("k", range(12))
+def test_posed_scene_conditions(oracle_lib, tmp_path, k):
+    """What the posed GPU tests rely on, by the C oracle alone at their 48x27: the
+    scene is still in view (>= 20 % of the pixels differ from the modal colour), at
+    most a quarter of the pixels raise, and a binding max_distance changes >= 5 %
+    of the pixels against the same pose with max_distance 10000 scale."""
+    import fuzz_scenes
+    seed = fuzz_scenes.POSED_SEEDS[k]
+    scale, offset, bind = fuzz_scenes.posed_parameters(seed)
+    w, c = fuzz_scenes.make_posed(seed, tmp_path, 48, 27)
+    sd, cd = config.load_scene(w, c)
+    assert sd.desc.max_distance == (9.0 if bind else 10000.0) * scale
+    fb, st, rc = Oracle(sd, cd).render(seed=seed)
+    raising = float((st != 0).mean())
+    in_view = _distinct_from_mode(fb)
+    print("posed seed %d (scale %g, offset %g, bind %d): raising %.4f, distinct from the mode %.4f"
+          % (seed, scale, offset, bind, raising, in_view))
+    assert raising <= 0.25, raising
+    assert in_view >= 0.20, in_view
+    if bind:
+        w2, c2 = fuzz_scenes.make_posed(seed, tmp_path, 48, 27, bind_distance=False)
+        sd2, cd2 = config.load_scene(w2, c2)
+        assert sd2.desc.max_distance == 10000.0 * scale
+        fb2, st2, _ = Oracle(sd2, cd2).render(seed=seed)
+        changed = float(((fb != fb2).any(axis=-1) | (st != st2)).mean())
+        print("posed seed %d: max_distance 9 scale changes %.4f of the pixels" % (seed, changed))
+        assert changed >= 0.05, changed
+        assert _distinct_from_mode(fb2) >= 0.20
