@@ -86,16 +86,12 @@ __device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int
     if (m.tex >= 0 && m.type != OBJ_BOX) {                // diffuse_rate * texture.color(*get_uv(intersection))
       uint32_t terr = 0;
       V3 tc;
-      if (m.type == OBJ_SPHERE) {                         // Sphere#get_uv (sphere.rb:111-120)
-        const Sphere64 sp = S.sph64[m.rec];
-        const V3 vec = vsub(hit, v3p(sp.c));
-        const double x0 = vdot(vec, v3p(m.gw_n)) / sp.r;
-        const double y0 = vdot(vec, v3p(m.east_n)) / sp.r;
-        const double z0 = vdot(vec, v3p(m.north_n)) / sp.r;
-        const double mm = sqrt(x0 * x0 + y0 * y0 + z0 * z0 + 2.0 * x0 + 1.0);
-        tc = texcolor(S, m.tex, m.hs, m.vs, m.u_off, m.v_off, (y0 / mm + 1.0) / 2.0, (-z0 / mm + 1.0) / 2.0, terr);
+      double u, v;
+      if (m.type == OBJ_SPHERE) {                         // (a negative sqrt argument: a NaN uv, zeros below)
+        double mm2;
+        sphere_uv(S, m, hit, u, v, mm2);
+        tc = texcolor(S, m.tex, m.hs, m.vs, m.u_off, m.v_off, u, v, terr);
       } else {                                            // Plane#get_uv (plane.rb:81-85)
-        double u, v;
         plane_uv(plane, hit, u, v);
         tc = texcolor(S, m.tex, m.hs, m.vs, 0.0, 0.0, u, v, terr);
       }

@@ -1546,6 +1546,80 @@ __device__ __forceinline__ void emit(Stack& st, Item& pend, bool& has, uint32_t&
   has = true;
 }
 
+// One light of local_lighting's loop (world_object.rb:51-74) from local_lights' `tot` (1 - covers, world.rb:72-80):
+// a lit light counts in nl and adds its colour, scaled by the clamped cosine, to lc.  The sums go in and out by
+// value: as reference parameters they cost k_render spilled registers.
+struct LightSum { V3 lc; int nl; };
+__device__ __forceinline__ LightSum light_term(const SceneDev& S, const LightDev& L, double tot, V3 hit, V3 nn, V3 lc,
+                                               int nl, uint32_t& err) {
+  const double area = tot > 0 ? tot : 0.0;
+  if (area > 0) {
+    nl++;
+    const double pw = S.sse_is_two ? area * area : rx_pow(area, S.sse);
+    const V3 lcol = vsc(v3p(L.color), pw / (double)S.n_light);
+    const V3 ll = vnorm(vsub(v3p(L.pos), hit), err);
+    double ldn = vdot(ll, nn);
+    if (ldn > 1) ldn = 1.0;
+    else if (ldn < 0) ldn = 0.0;
+    lc = vadd(lc, vsc(lcol, ldn));
+  }
+  return {lc, nl};
+}
+
+// Sphere#get_uv (sphere.rb:111-120).  mm2: its Math.sqrt's argument (a negative one: the caller's raise policy).
+__device__ __forceinline__ void sphere_uv(const SceneDev& S, const Material& m, V3 hit, double& u, double& v,
+                                          double& mm2) {
+  const Sphere64 sp = S.sph64[m.rec];
+  const V3 vec = vsub(hit, v3p(sp.c));
+  const double x0 = vdot(vec, v3p(m.gw_n)) / sp.r;
+  const double y0 = vdot(vec, v3p(m.east_n)) / sp.r;
+  const double z0 = vdot(vec, v3p(m.north_n)) / sp.r;
+  mm2 = x0 * x0 + y0 * y0 + z0 * z0 + 2.0 * x0 + 1.0;
+  const double mm = sqrt(mm2);
+  u = (y0 / mm + 1.0) / 2.0;
+  v = (-z0 / mm + 1.0) / 2.0;
+}
+
+// local_lighting's colour (world_object.rb:51-74) from the light loop's sum lc over nl lit lights, texture filter.
+__device__ __forceinline__ V3 leaf_color(const SceneDev& S, const Material& m, V3 hit, V3 lc, int nl, uint32_t& err) {
+  lc = vdiv(lc, (double)nl);
+  V3 color;
+  if (m.type == OBJ_BOX) {
+    color = vadd(vmul(lc, v3p(m.diffuse)), v3p(m.ambient));
+  } else {
+    V3 filter = v3(1.0, 1.0, 1.0);
+    if (m.tex >= 0) {
+      if (m.type == OBJ_SPHERE) {
+        double u, v, mm2;
+        sphere_uv(S, m, hit, u, v, mm2);
+        if (mm2 < 0) seterr(err, ERR_DOMAIN);
+        filter = vmul(texcolor(S, m.tex, m.hs, m.vs, m.u_off, m.v_off, u, v, err), filter);
+      } else {
+        double u, v;
+        plane_uv(S.planes + (size_t)m.rec * PLANE_GEO, hit, u, v);
+        filter = vmul(texcolor(S, m.tex, m.hs, m.vs, 0.0, 0.0, u, v, err), filter);
+      }
+    }
+    color = vadd(vmul(vmul(lc, v3p(m.diffuse)), filter), v3p(m.ambient));
+  }
+  return color;
+}
+
+// WorldObject#path_tracing's frame (world_object.rb:76-90) around n's unit vector nn, and child k's direction.
+__device__ __forceinline__ void pt_basis(V3 n, V3 nn, V3& left, V3& up, uint32_t& err) {
+  left = vnorm(vertical_vector(n, err), err);
+  up = vcross(nn, left);
+}
+__device__ __forceinline__ V3 pt_dir(uint64_t seed, int x, int y, int sample, uint64_t path, int k, V3 nn, V3 left,
+                                     V3 up) {
+  const double theta = rand01(seed, x, y, sample, path, 2 * k) * PI / 2.0;
+  const double phi = rand01(seed, x, y, sample, path, 2 * k + 1) * PI * 2.0;
+  double sth, cth, sph, cph;
+  RTX_SINCOS(theta, &sth, &cth);
+  RTX_SINCOS(phi, &sph, &cph);
+  return vadd(vsc(nn, sth), vsc(vadd(vsc(left, cph), vsc(up, sph)), cth));
+}
+
 // The rest of rt_map once every light's lit area is known (ray_tracer.rb:80-158):
 // reflection / refraction children, then path-tracing children (no lit light)
 // or the local-lighting leaf.  Returns true with the next ray in `cur`.
@@ -1572,48 +1646,16 @@ RTX_SHADE_FN bool shade_finish(const SceneDev& S, const CameraDev& cam, uint64_t
     // WorldObject#path_tracing (world_object.rb:76-90) from hit + delta
     const int pt = cam.pt;
     const V3 att = vmul(cur.att, vdiv(v3p(m.diffuse), (double)pt));
-    const V3 front = nn;
-    const V3 left = vnorm(vertical_vector(n, err), err);
-    const V3 up = vcross(front, left);
+    V3 left, up;
+    pt_basis(n, nn, left, up, err);
     Ray r;
     r.o = vadd(hit, delta);
     for (int k = 0; k < pt; k++) {
-      const double theta = rand01(seed, x, y, sample, cur.path, 2 * k) * PI / 2.0;
-      const double phi = rand01(seed, x, y, sample, cur.path, 2 * k + 1) * PI * 2.0;
-      double sth, cth, sph, cph;
-      RTX_SINCOS(theta, &sth, &cth);
-      RTX_SINCOS(phi, &sph, &cph);
-      r.d = vadd(vsc(front, sth), vsc(vadd(vsc(left, cph), vsc(up, sph)), cth));
+      r.d = pt_dir(seed, x, y, sample, cur.path, k, nn, left, up);
       emit(st, pend, has, err, r, att, cur.path * R + 3 + (uint64_t)k, cur.depth - 1);
     }
   } else {
-    lc = vdiv(lc, (double)nl);
-    V3 color;
-    if (m.type == OBJ_BOX) {
-      color = vadd(vmul(lc, v3p(m.diffuse)), v3p(m.ambient));
-    } else {
-      V3 filter = v3(1.0, 1.0, 1.0);
-      if (m.tex >= 0) {
-        if (m.type == OBJ_SPHERE) {                   // Sphere#get_uv (sphere.rb:111-120)
-          const Sphere64 sp = S.sph64[m.rec];
-          const V3 vec = vsub(hit, v3p(sp.c));
-          const double x0 = vdot(vec, v3p(m.gw_n)) / sp.r;
-          const double y0 = vdot(vec, v3p(m.east_n)) / sp.r;
-          const double z0 = vdot(vec, v3p(m.north_n)) / sp.r;
-          const double mm2 = x0 * x0 + y0 * y0 + z0 * z0 + 2.0 * x0 + 1.0;
-          if (mm2 < 0) seterr(err, ERR_DOMAIN);
-          const double mm = sqrt(mm2);
-          filter = vmul(texcolor(S, m.tex, m.hs, m.vs, m.u_off, m.v_off, (y0 / mm + 1.0) / 2.0,
-                                 (-z0 / mm + 1.0) / 2.0, err), filter);
-        } else {
-          double u, v;
-          plane_uv(S.planes + (size_t)m.rec * PLANE_GEO, hit, u, v);
-          filter = vmul(texcolor(S, m.tex, m.hs, m.vs, 0.0, 0.0, u, v, err), filter);
-        }
-      }
-      color = vadd(vmul(vmul(lc, v3p(m.diffuse)), filter), v3p(m.ambient));
-    }
-    add_leaf(sum, vmul(cur.att, color), err);
+    add_leaf(sum, vmul(cur.att, leaf_color(S, m, hit, lc, nl, err)), err);
   }
   if (has) cur = pend;
   return has;

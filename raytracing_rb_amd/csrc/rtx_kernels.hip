@@ -320,18 +320,9 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
     } else {
       // World#local_lights (world.rb:72-80) fused with the light loop of
       // WorldObject#local_lighting (world_object.rb:51-74): same order, same sums.
-      const double area = total > 0 ? total : 0.0;
-      if (area > 0) {
-        const LightDev& L = S.light[li];
-        nl++;
-        const double pw = S.sse_is_two ? area * area : rx_pow(area, S.sse);
-        const V3 lcol = vsc(v3p(L.color), pw / (double)S.n_light);
-        const V3 ll = vnorm(vsub(v3p(L.pos), hit), err);
-        double ldn = vdot(ll, nn);
-        if (ldn > 1) ldn = 1.0;
-        else if (ldn < 0) ldn = 0.0;
-        lc = vadd(lc, vsc(lcol, ldn));
-      }
+      const LightSum ls = light_term(S, S.light[li], total, hit, nn, lc, nl, err);
+      lc = ls.lc;
+      nl = ls.nl;
       li++;
     }
     if (li < S.n_light) {                    // next light: a SHADOW query from hit + delta

@@ -112,6 +112,54 @@ struct LvWgStamps {
   }
 };
 
+// A wave's shader-clock time in each of a level kernel's 6 phases, its chunks
+// and its lanes with a ray, an EXTEND walk, a hit (per chunk, summed), added
+// to rtx_stamps and the level's row of rtx_stamps_lv when the wave ends.
+// Compiles to nothing unless RTX_STAMPS.
+struct LvStamps {
+#if RTX_STAMPS
+  unsigned long long tS[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, nchunks = 0, nA = 0, nE = 0, nS = 0;
+#endif
+  // the clock restarts; `claimed` false: no new chunk (k_level_c's final flush)
+  __device__ __forceinline__ void begin_chunk(bool claimed = true) {
+#if RTX_STAMPS
+    t0 = stamp();
+    if (claimed) nchunks++;
+#endif
+  }
+  // the time since the last stamp goes to phase k
+  __device__ __forceinline__ void mark(int k) {
+#if RTX_STAMPS
+    const unsigned long long t1 = stamp();
+    tS[k] += t1 - t0;
+    t0 = t1;
+#endif
+  }
+  // all lanes call it
+  __device__ __forceinline__ void count(bool active, bool ext, bool shade) {
+#if RTX_STAMPS
+    nA += __popcll(__ballot(active));
+    nE += __popcll(__ballot(ext));
+    nS += __popcll(__ballot(shade));
+#endif
+  }
+  __device__ __forceinline__ void flush(int level) {
+#if RTX_STAMPS
+    if (__lane_id() != 0) return;
+    for (int k = 0; k < 6; k++) atomicAdd(&rtx_stamps[k], tS[k]);
+    atomicAdd(&rtx_stamps[6], nchunks);
+    atomicAdd(&rtx_stamps[7], 1ull);
+    atomicAdd(&rtx_stamps[8], nA);
+    atomicAdd(&rtx_stamps[9], nE);
+    atomicAdd(&rtx_stamps[10], nS);
+    unsigned long long* lv = rtx_stamps_lv + 8 * (level < 7 ? level : 7);
+    for (int k = 0; k < 6; k++) atomicAdd(&lv[k], tS[k]);
+    atomicAdd(&lv[6], nchunks);
+    atomicAdd(&lv[7], nS);
+#endif
+  }
+};
+
 int levels_rec_bytes(int n_light) {
   const int nl = n_light > 1 ? n_light : 1;
   return (8 + 24 * nl + 15) & ~15;       // {meta, first child} + one leaf per fired light
@@ -175,6 +223,19 @@ __device__ __forceinline__ void lv_store_ray(const KParams& p, double* dst, cons
   q[4] = make_double2(att.z, __builtin_bit_cast(double, path));
   q[5] = make_double2(__builtin_bit_cast(double, (uint64_t)(uint32_t)root | (uint64_t)(uint32_t)sample << 32),
                       __builtin_bit_cast(double, (uint64_t)(uint32_t)x | (uint64_t)(uint32_t)y << 32));
+}
+
+// A staged ray record's (lv_store_ray) origin and direction, and its
+// attenuation with the 16-B word `e` that ends it (lv_ray_tail reads the rest).
+__device__ __forceinline__ void lv_unpack_ray(const double2* q, V3& o, V3& d) {
+  const double2 a = q[0], b = q[1], c = q[2];
+  o = v3(a.x, a.y, b.x);
+  d = v3(b.y, c.x, c.y);
+}
+__device__ __forceinline__ V3 lv_unpack_att(const double2* q, double2& e) {
+  const double2 d = q[3];
+  e = q[4];
+  return v3(d.x, d.y, e.x);
 }
 
 // A staged ray's path, root item and RNG key from the record's last 16-B
@@ -608,10 +669,9 @@ __device__ __forceinline__ void lv_ray(const KParams& p, int level, uint32_t idx
     return;
   }
   const double2* q = reinterpret_cast<const double2*>(lv_src(p, level) + (size_t)idx * p.lv_ray_dbl);
-  const double2 a = q[0], b = q[1], c = q[2], d = q[3], e = q[4];
-  cur.ray.o = v3(a.x, a.y, b.x);
-  cur.ray.d = v3(b.y, c.x, c.y);
-  cur.att = v3(d.x, d.y, e.x);
+  double2 e;
+  lv_unpack_ray(q, cur.ray.o, cur.ray.d);
+  cur.att = lv_unpack_att(q, e);
   lv_ray_tail(p, q, e, cur.path, root, x, y, sample);
 }
 
@@ -625,12 +685,134 @@ __device__ __forceinline__ void lv_ray_key(const KParams& p, int root, int& x, i
   sample = ip.sample;
 }
 
+// What the first half of rt_map leaves of a level's ray (lv_first_half).
+struct LvFirst {
+  Item cur;                       // the ray; its attenuation and path where lv_ray loaded them
+  int root, x, y, sample;         // the tree's root item and RNG key, where lv_ray loaded them
+  char* rec;                      // the ray's tree record (the highlight leaves are in it)
+  uint32_t errA, errL;            // raises of the highlights, of the walk
+  int nleaf, besti;
+  V3 hit;
+  bool hin, ext, shade;           // ext: the ray was walked; shade: and hit object besti
+};
+
+// The first half of rt_map for one ray of a level (ray_tracer.rb:52-77 and
+// World#intersect, world.rb:37-59): the ray of queue slot `slot` (dense index
+// i), rt_map's cutoff, room in the record arena (`active` cleared for tile
+// padding and for a ray without room: no record), the highlight leaves with
+// lit_area's raise deferred (lv_hl_defer), the nearest-hit walk.  All lanes
+// of the wave call it.  st: the caller's phase stamps, or null.
+// k_level and k_lv_trace.  k_level_c keeps its own first half (it loads a
+// staged child lazily) and its own hit frame and shadow loop: built from these
+// functions it rendered the same bits, but C4 (k_level_c<SPH_BVH_QLDS>, at
+// 256 VGPRs) 0.8 % slower, 262.4 against 260.5 ms, 1.5 ms of it the first half.
+template <int SPH, int BS>
+__device__ __forceinline__ void lv_first_half(const KParams& p, char* lds, int level, uint32_t slot, uint32_t i,
+                                              uint32_t base, int depth, bool& active, LvFirst& f, LvStamps* st) {
+  const SceneDev& S = p.scene;
+  f.root = f.x = f.y = f.sample = 0;
+  bool alive = false;
+  if (active) {
+    bool valid;
+    lv_ray(p, level, slot, f.cur, f.root, f.x, f.y, f.sample, valid);
+    if (level == 0) p.lv_redo_of[i] = -1;     // no overflow yet (lv_redo)
+    active = valid;                           // tile padding: no record
+    alive = valid && (level > 0 || !(depth <= 0 || vr(f.cur.att) < 0.0001));   // rt_map's cutoff (ray_tracer.rb:52)
+    if (active && base + i >= p.lv_lcap) {    // no room for this ray's record
+      lv_redo(p, f.root);
+      active = alive = false;
+    }
+  }
+  f.rec = p.lv_rec + (size_t)(base + i) * p.lv_rec_bytes;
+  double* leafp = reinterpret_cast<double*>(f.rec + 8);
+
+  // ---- rt_map: highlights (ray_tracer.rb:60-75)
+  f.errA = f.errL = 0;
+  f.nleaf = 0;
+  bool fired = false, hl_defer = false;
+  if (alive)
+    fired = highlight_leaves(S, f.cur, [&](V3 c) {
+      leafp[3 * f.nleaf] = c.x;
+      leafp[3 * f.nleaf + 1] = c.y;
+      leafp[3 * f.nleaf + 2] = c.z;
+      f.nleaf++;
+    }, f.errA, [&](V3, V3, double, int) {       // lit_area's raise: deferred to k_hl_raise
+      hl_defer = true;
+      return false;
+    });
+  lv_hl_defer(p, hl_defer, f.cur.ray, base + i, [&] { return f.root; });
+  if (st) st->mark(0);
+  // ---- World#intersect (world.rb:37-59)
+  f.ext = alive && !fired;
+  double best = S.max_distance, total = 0.0;
+  f.besti = -1;
+  f.hit = v3(0.0, 0.0, 0.0);
+  f.hin = true;
+  if (f.ext)
+    lv_walk<SPH, BS>(p, lds, true, f.cur.ray.o, f.cur.ray.d, f.hit, 0.0, best, f.besti, f.hit, f.hin, total, f.errL,
+                     XR_NONE);
+  f.shade = f.ext && f.besti >= 0;
+  if (st) {
+    st->count(active, f.ext, f.shade);
+    st->mark(1);
+  }
+}
+
+// The tree record of a ray that ends in its first half (cut off, fired, or
+// no hit): its highlight leaves, no children.
+__device__ __forceinline__ void lv_end_record(const LvFirst& f) {
+  const uint32_t err = f.errA ? f.errA : f.errL;
+  *reinterpret_cast<uint2*>(f.rec) = make_uint2((err & 0xffu) | ((uint32_t)f.nleaf << 8), 0u);
+}
+
+// intersect_parameters' frame of a hit (world_object.rb:121-137): hit_info's
+// delta and normal, the unit normal, the cosine, and the shadow rays' target.
+struct LvFrame {
+  V3 delta, nrm, nn, qo;
+  double c;
+};
+// (k_level_c's own copy reads the LDS-staged materials of SPH_BVH_LDSX.)
+__device__ __forceinline__ void lv_hit_frame(const SceneDev& S, bool shade, int besti, const Ray& ray, V3& hit,
+                                             bool& hin, LvFrame& fr, uint32_t& errS) {
+  fr.delta = fr.nrm = fr.nn = hit;
+  fr.c = 0.0;
+  if (shade) {
+    hit_info(S, besti, ray, hit, fr.delta, fr.nrm, hin);
+    fr.nn = vnorm(fr.nrm, errS);              // n.normalize (world_object.rb:123)
+    fr.c = vcos(ray.d, fr.nrm, errS);         // ray.front.cos(-n): same bits as cos(n)
+  }
+  fr.qo = vadd(hit, fr.delta);                // the shadow rays' target point (world.rb:76)
+}
+
+// World#local_lights (world.rb:72-80) fused with local_lighting's light loop
+// (world_object.rb:51-74): one SHADOW walk per light from qo, then its term.
+template <int SPH, int BS, int XR>
+__device__ __forceinline__ LightSum lv_shadow_lights(const KParams& p, char* lds, bool shade, V3 qo, V3 hit, V3 nn,
+                                                     uint32_t& errL, uint32_t& errP) {
+  const SceneDev& S = p.scene;
+  LightSum ls = {v3(0.0, 0.0, 0.0), 0};
+  for (int li = 0; li < S.n_light; li++) {
+    if (!shade) continue;
+    const LightDev& L = S.light[li];
+    const V3 qL = v3p(L.pos);
+    double tot = 1.0;
+    double b2 = 0.0;
+    int bi2 = -1;
+    V3 h2 = qo;
+    bool in2 = true;
+    lv_walk<SPH, BS>(p, lds, false, qo, vsub(qL, qo), qL, L.radius, b2, bi2, h2, in2, tot, errL, XR, li);
+    ls = light_term(S, L, tot, hit, nn, ls.lc, ls.nl, errP);
+  }
+  return ls;
+}
+
 // rt_map's tail once the lit areas are known (ray_tracer.rb:80-158): which
 // children pass the cutoff (:52) at depth - 1, their slots in the next level
 // (slice of this wave), the children in the reference's push order, else the
-// local_lighting leaf; then the ray's tree record.  Shared by k_level and
-// k_lv_shade; every lane of the wave calls it (the slot allocation is a wave
-// operation).  errA/errS/errL/errP: the raises so far, in rt_map's order.
+// local_lighting leaf (leaf_color); then the ray's tree record.  The tail of
+// every variant: k_level, k_level_c's second half, k_lv_shade.  Every lane of
+// the wave calls it (the slot allocation is a wave operation).
+// errA/errS/errL/errP: the raises so far, in rt_map's order.
 __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice, bool shade, bool active,
                                           const Item& cur, int root, int x, int y, int sample, int besti, bool hin,
                                           V3 hit, V3 delta, V3 nrm, V3 nn, double c, V3 lc, int nl, char* rec,
@@ -692,34 +874,7 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
       if (!errS) errS = ERR_ZERO_VEC;
     }
     if (nl != 0) {
-      // WorldObject#local_lighting's colour (world_object.rb:51-74), texture filter
-      lc = vdiv(lc, (double)nl);
-      V3 color;
-      if (m->type == OBJ_BOX) {
-        color = vadd(vmul(lc, v3p(m->diffuse)), v3p(m->ambient));
-      } else {
-        V3 filter = v3(1.0, 1.0, 1.0);
-        if (m->tex >= 0) {
-          if (m->type == OBJ_SPHERE) {             // Sphere#get_uv (sphere.rb:111-120)
-            const Sphere64 sp = S.sph64[m->rec];
-            const V3 vec = vsub(hit, v3p(sp.c));
-            const double x0 = vdot(vec, v3p(m->gw_n)) / sp.r;
-            const double y0 = vdot(vec, v3p(m->east_n)) / sp.r;
-            const double z0 = vdot(vec, v3p(m->north_n)) / sp.r;
-            const double mm2 = x0 * x0 + y0 * y0 + z0 * z0 + 2.0 * x0 + 1.0;
-            if (mm2 < 0) seterr(errP, ERR_DOMAIN);
-            const double mm = sqrt(mm2);
-            filter = vmul(texcolor(S, m->tex, m->hs, m->vs, m->u_off, m->v_off, (y0 / mm + 1.0) / 2.0,
-                                   (-z0 / mm + 1.0) / 2.0, errP), filter);
-          } else {
-            double u, v;
-            plane_uv(S.planes + (size_t)m->rec * PLANE_GEO, hit, u, v);
-            filter = vmul(texcolor(S, m->tex, m->hs, m->vs, 0.0, 0.0, u, v, errP), filter);
-          }
-        }
-        color = vadd(vmul(vmul(lc, v3p(m->diffuse)), filter), v3p(m->ambient));
-      }
-      const V3 leaf = vmul(cur.att, color);
+      const V3 leaf = vmul(cur.att, leaf_color(S, *m, hit, lc, nl, errP));
       double* leafp = reinterpret_cast<double*>(rec + 8);
       leafp[0] = leaf.x;
       leafp[1] = leaf.y;
@@ -751,18 +906,13 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
       // sites (vertical_vector's zero test, the normalize of a vector with a
       // component 1) cannot fire unless n.normalize raised first (errS).
       const V3 att = vmul(cur.att, vdiv(v3p(m->diffuse), (double)pt));
-      const V3 left = vnorm(vertical_vector(nrm, errP), errP);
-      const V3 up = vcross(nn, left);
+      V3 left, up;
+      pt_basis(nrm, nn, left, up, errP);
       Ray r;
       r.o = vadd(hit, delta);
       lv_ray_key(p, root, x, y, sample);
       for (int k = 0; k < pt; k++) {
-        const double theta = rand01(p.seed, x, y, sample, cur.path, 2 * k) * PI / 2.0;
-        const double phi = rand01(p.seed, x, y, sample, cur.path, 2 * k + 1) * PI * 2.0;
-        double sth, cth, sph, cph;
-        RTX_SINCOS(theta, &sth, &cth);
-        RTX_SINCOS(phi, &sph, &cph);
-        r.d = vadd(vsc(nn, sth), vsc(vadd(vsc(left, cph), vsc(up, sph)), cth));
+        r.d = pt_dir(p.seed, x, y, sample, cur.path, k, nn, left, up);
         if (mask >> (2 + k) & 1u) put(r, att, cur.path * R + 3 + (uint64_t)k);
       }
     }
@@ -795,125 +945,29 @@ __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
   LvSched sched(p.lv_ctl->claim[0][level], p.lv_static_pct);
   const int slice = sched.wave_id() & (LV_SLICES - 1);
 
-  unsigned long long tS[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, t1, nchunks = 0;   // RTX_STAMPS diagnostic build only
-  unsigned long long nA = 0, nE = 0, nS = 0;  // lanes with a ray, an EXTEND walk, a hit (per chunk, summed)
-#define RTX_LV_STAMP(k)  \
-  if (RTX_STAMPS) {      \
-    t1 = stamp();        \
-    tS[k] += t1 - t0;    \
-    t0 = t1;             \
-  }
+  LvStamps st;                                // RTX_STAMPS diagnostic build only
   uint32_t chunk;
   const uint32_t nch = lv_chunks(p, in, level);
   while (sched.claim(p, nch, chunk)) {
-    if (RTX_STAMPS) {
-      t0 = stamp();
-      nchunks++;
-    }
+    st.begin_chunk();
     uint32_t slot, i;
     bool active = lv_chunk_item(p, in, level, chunk, slot, i);   // i: the ray's dense index in the level
-    // ---- the ray: a camera sample (level 0) or a staged child
-    Item cur;
-    int root = 0, x = 0, y = 0, sample = 0;
-    bool alive = false;
-    if (active) {
-      bool valid;
-      lv_ray(p, level, slot, cur, root, x, y, sample, valid);
-      if (level == 0) p.lv_redo_of[i] = -1;   // no overflow yet (lv_redo)
-      active = valid;                         // tile padding: no record
-      alive = valid && (level > 0 || !(depth <= 0 || vr(cur.att) < 0.0001));   // rt_map's cutoff (ray_tracer.rb:52)
-      if (active && base + i >= p.lv_lcap) {  // no room for this ray's record
-        lv_redo(p, root);
-        active = alive = false;
-      }
-    }
-    char* rec = p.lv_rec + (size_t)(base + i) * p.lv_rec_bytes;
-    double* leafp = reinterpret_cast<double*>(rec + 8);
-
-    // ---- rt_map: highlights (ray_tracer.rb:60-75)
-    uint32_t errA = 0, errS = 0, errL = 0, errP = 0;
-    int nleaf = 0;
-    bool fired = false, hl_defer = false;
-    if (alive)
-      fired = highlight_leaves(S, cur, [&](V3 c) {
-        leafp[3 * nleaf] = c.x;
-        leafp[3 * nleaf + 1] = c.y;
-        leafp[3 * nleaf + 2] = c.z;
-        nleaf++;
-      }, errA, [&](V3, V3, double, int) {         // lit_area's raise: deferred to k_hl_raise
-        hl_defer = true;
-        return false;
-      });
-    lv_hl_defer(p, hl_defer, cur.ray, base + i, [&] { return root; });
-    RTX_LV_STAMP(0)
-    // ---- World#intersect (world.rb:37-59)
-    const bool ext = alive && !fired;
-    double best = S.max_distance, total = 0.0;
-    int besti = -1;
-    V3 hit = v3(0.0, 0.0, 0.0);
-    bool hin = true;
-    if (ext) lv_walk<SPH, BS>(p, lds, true, cur.ray.o, cur.ray.d, hit, 0.0, best, besti, hit, hin, total, errL, XR_NONE);
-    const bool shade = ext && besti >= 0;
-    if (RTX_STAMPS) {
-      nA += __popcll(__ballot(active));
-      nE += __popcll(__ballot(ext));
-      nS += __popcll(__ballot(shade));
-    }
-    RTX_LV_STAMP(1)
-    V3 delta = hit, nrm = hit, nn = hit;
-    double c = 0.0;
-    if (shade) {
-      hit_info(S, besti, cur.ray, hit, delta, nrm, hin);
-      nn = vnorm(nrm, errS);                  // n.normalize (world_object.rb:123)
-      c = vcos(cur.ray.d, nrm, errS);         // ray.front.cos(-n): same bits as cos(n)
-    }
-    const V3 qo = vadd(hit, delta);           // the shadow rays' target point (world.rb:76)
-    RTX_LV_STAMP(2)
-    // ---- World#local_lights (world.rb:72-80) fused with local_lighting's
-    // light loop (world_object.rb:51-74): one SHADOW walk per light.
-    V3 lc = v3(0.0, 0.0, 0.0);
-    int nl = 0;
-    for (int li = 0; li < S.n_light; li++) {
-      if (!shade) continue;
-      const LightDev& L = S.light[li];
-      const V3 qL = v3p(L.pos);
-      double tot = 1.0;
-      double b2 = 0.0;
-      int bi2 = -1;
-      V3 h2 = qo;
-      bool in2 = true;
-      lv_walk<SPH, BS>(p, lds, false, qo, vsub(qL, qo), qL, L.radius, b2, bi2, h2, in2, tot, errL, XR, li);
-      const double area = tot > 0 ? tot : 0.0;
-      if (area > 0) {
-        nl++;
-        const double pw = S.sse_is_two ? area * area : rx_pow(area, S.sse);
-        const V3 lcol = vsc(v3p(L.color), pw / (double)S.n_light);
-        const V3 ll = vnorm(vsub(v3p(L.pos), hit), errP);
-        double ldn = vdot(ll, nn);
-        if (ldn > 1) ldn = 1.0;
-        else if (ldn < 0) ldn = 0.0;
-        lc = vadd(lc, vsc(lcol, ldn));
-      }
-    }
-    RTX_LV_STAMP(3)
-    lv_finish(p, level, slice, shade, active, cur, root, x, y, sample, besti, hin, hit, delta, nrm, nn, c, lc, nl, rec,
-              nleaf, errA, errS, errL, errP, shade ? &S.mat[besti] : S.mat, false, p.lv_sort && level + 1 >= p.lv_sort);
-    RTX_LV_STAMP(5)
+    LvFirst f;
+    lv_first_half<SPH, BS>(p, lds, level, slot, i, base, depth, active, f, &st);
+    uint32_t errS = 0, errP = 0;
+    LvFrame fr;
+    lv_hit_frame(S, f.shade, f.besti, f.cur.ray, f.hit, f.hin, fr, errS);
+    st.mark(2);
+    const LightSum ls = lv_shadow_lights<SPH, BS, XR>(p, lds, f.shade, fr.qo, f.hit, fr.nn, f.errL, errP);
+    st.mark(3);
+    // (a ray that ends in its first half gets its record here too: no children, its highlight leaves)
+    lv_finish(p, level, slice, f.shade, active, f.cur, f.root, f.x, f.y, f.sample, f.besti, f.hin, f.hit, fr.delta,
+              fr.nrm, fr.nn, fr.c, ls.lc, ls.nl, f.rec, f.nleaf, f.errA, errS, f.errL, errP,
+              f.shade ? &S.mat[f.besti] : S.mat, false, p.lv_sort && level + 1 >= p.lv_sort);
+    st.mark(5);
   }
-#undef RTX_LV_STAMP
   wgs.end(level);
-  if (RTX_STAMPS && __lane_id() == 0) {
-    for (int k = 0; k < 6; k++) atomicAdd(&rtx_stamps[k], tS[k]);
-    atomicAdd(&rtx_stamps[6], nchunks);
-    atomicAdd(&rtx_stamps[7], 1ull);
-    atomicAdd(&rtx_stamps[8], nA);
-    atomicAdd(&rtx_stamps[9], nE);
-    atomicAdd(&rtx_stamps[10], nS);
-    unsigned long long* lv = rtx_stamps_lv + 8 * (level < 7 ? level : 7);
-    for (int k = 0; k < 6; k++) atomicAdd(&lv[k], tS[k]);
-    atomicAdd(&lv[6], nchunks);
-    atomicAdd(&lv[7], nS);
-  }
+  st.flush(level);
 }
 
 template <int SPH, int BS, int XR>
@@ -976,21 +1030,13 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
   bool got = true;
   const uint32_t nch = lv_chunks(p, in, level);
 
-  unsigned long long tS[6] = {0, 0, 0, 0, 0, 0}, t0 = 0, t1, nchunks = 0;   // RTX_STAMPS diagnostic build only
-  unsigned long long nA = 0, nE = 0, nS = 0;
-#define RTX_LV_STAMP(k)  \
-  if (RTX_STAMPS) {      \
-    t1 = stamp();        \
-    tS[k] += t1 - t0;    \
-    t0 = t1;             \
-  }
+  LvStamps st;                                // RTX_STAMPS diagnostic build only
   while (true) {
     {                                         // first half, chunk by chunk, until 64 hits are parked
       uint32_t chunk = 0;
       if (got) got = sched.claim(p, nch, chunk);   // (never again once exhausted)
-      if (RTX_STAMPS) t0 = stamp();
+      st.begin_chunk(got);
       if (got) {
-        if (RTX_STAMPS) nchunks++;
         // ---- first half: the ray, rt_map's cutoff, highlights, World#intersect
         uint32_t slot, i;
         bool active = lv_chunk_item(p, in, level, chunk, slot, i);
@@ -1035,11 +1081,11 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
             leafp[3 * nleaf + 2] = c.z;
             nleaf++;
           }, errA, [&](V3, V3, double, int) {         // lit_area's raise: deferred to k_hl_raise
-        hl_defer = true;
-        return false;
-      });
+            hl_defer = true;
+            return false;
+          });
         lv_hl_defer(p, hl_defer, cur.ray, base + i, [&] { return level == 0 ? root : lv_ray_root(p, qs); });
-        RTX_LV_STAMP(0)
+        st.mark(0);
         const bool ext = alive && !fired;
         double best = S.max_distance, total = 0.0;
         int besti = -1;
@@ -1047,12 +1093,8 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
         bool hin = true;
         if (ext) lv_walk<SPH, BS>(p, lds, true, cur.ray.o, cur.ray.d, hit, 0.0, best, besti, hit, hin, total, errL, XR_NONE);
         const bool shade = ext && besti >= 0;
-        if (RTX_STAMPS) {
-          nA += __popcll(__ballot(active));
-          nE += __popcll(__ballot(ext));
-          nS += __popcll(__ballot(shade));
-        }
-        RTX_LV_STAMP(1)
+        st.count(active, ext, shade);
+        st.mark(1);
         if (active && !shade) {                 // the ray ends here: its record (k_level's, no children)
           const uint32_t err = errA ? errA : errL;
           *reinterpret_cast<uint2*>(rec) = make_uint2((err & 0xffu) | ((uint32_t)nleaf << 8), 0u);
@@ -1078,7 +1120,7 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
               double, (uint64_t)((uint32_t)besti | (hin ? 0x80000000u : 0u)) | (uint64_t)((errA & 0xffu) | (errL & 0xffu) << 8) << 32);
         }
         pend += (uint32_t)__popcll(hm);
-        RTX_LV_STAMP(4)
+        st.mark(4);
       }
       if (pend < 64 && (got || pend == 0)) {
         if (!got) break;                        // no chunk left and nothing parked
@@ -1121,20 +1163,16 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
         }
       } else {                                // the staged child at its queue slot (lv_ray)
         const double2* q = reinterpret_cast<const double2*>(lv_src(p, level) + (size_t)(is >> 32) * p.lv_ray_dbl);
-        if (RF != LV_RING_FIELDS) {
-          const double2 a = q[0], b = q[1], c = q[2];
-          cur.ray.o = v3(a.x, a.y, b.x);
-          cur.ray.d = v3(b.y, c.x, c.y);
-        }
-        const double2 d = q[3], e = q[4];
-        cur.att = v3(d.x, d.y, e.x);
+        if (RF != LV_RING_FIELDS) lv_unpack_ray(q, cur.ray.o, cur.ray.d);
+        double2 e;
+        cur.att = lv_unpack_att(q, e);
         lv_ray_tail(p, q, e, cur.path, root, x, y, sample);
       }
     }
     head = (head + take) & (LV_RING - 1);
     pend -= take;
     char* rec = p.lv_rec + (size_t)(base + i) * p.lv_rec_bytes;
-    RTX_LV_STAMP(4)
+    st.mark(4);
     V3 delta = hit, nrm = hit, nn = hit;
     double c = 0.0;
     // the hit object's material (and sphere record): LDS copies when staged
@@ -1151,7 +1189,7 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
       c = vcos(cur.ray.d, nrm, errS);         // ray.front.cos(-n): same bits as cos(n)
     }
     const V3 qo = vadd(hit, delta);           // the shadow rays' target point (world.rb:76)
-    RTX_LV_STAMP(2)
+    st.mark(2);
     V3 lc = v3(0.0, 0.0, 0.0);
     int nl = 0;
     for (int li = 0; li < S.n_light; li++) {  // World#local_lights + local_lighting's light loop
@@ -1176,25 +1214,13 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
         lc = vadd(lc, vsc(lcol, ldn));
       }
     }
-    RTX_LV_STAMP(3)
+    st.mark(3);
     lv_finish(p, level, slice, shade, shade, cur, root, x, y, sample, besti, hin, hit, delta, nrm, nn, c, lc, nl, rec, 0,
               errA, errS, errL, errP, m, LAST, SORT);
-    RTX_LV_STAMP(5)
+    st.mark(5);
   }
-#undef RTX_LV_STAMP
   wgs.end(level);
-  if (RTX_STAMPS && __lane_id() == 0) {
-    for (int k = 0; k < 6; k++) atomicAdd(&rtx_stamps[k], tS[k]);
-    atomicAdd(&rtx_stamps[6], nchunks);
-    atomicAdd(&rtx_stamps[7], 1ull);
-    atomicAdd(&rtx_stamps[8], nA);
-    atomicAdd(&rtx_stamps[9], nE);
-    atomicAdd(&rtx_stamps[10], nS);
-    unsigned long long* lv = rtx_stamps_lv + 8 * (level < 7 ? level : 7);
-    for (int k = 0; k < 6; k++) atomicAdd(&lv[k], tS[k]);
-    atomicAdd(&lv[6], nchunks);
-    atomicAdd(&lv[7], nS);
-  }
+  st.flush(level);
 }
 
 template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
@@ -1247,63 +1273,28 @@ __global__ __launch_bounds__(BS, RTX_LV_WALK_WPS) void k_lv_trace(KParams p, int
     uint32_t s, off, i;
     bool active = in.item(chunk, s, off, i);
     const uint32_t slot = level == 0 ? i : (s << p.lv_slice_log2) + off;
-    bool alive = false;
-    Item cur;
-    int root = 0, x = 0, y = 0, sample = 0;
-    if (active) {
-      bool valid;
-      lv_ray(p, level, slot, cur, root, x, y, sample, valid);
-      if (level == 0) p.lv_redo_of[i] = -1;   // no overflow yet (lv_redo)
-      active = valid;                         // tile padding: no record
-      alive = valid && (level > 0 || !(depth <= 0 || vr(cur.att) < 0.0001));   // rt_map's cutoff (ray_tracer.rb:52)
-      if (active && base + i >= p.lv_lcap) {  // no room for this ray's record
-        lv_redo(p, root);
-        active = alive = false;
-      }
-    }
-    char* rec = p.lv_rec + (size_t)(base + i) * p.lv_rec_bytes;
-    double* leafp = reinterpret_cast<double*>(rec + 8);
-    uint32_t errA = 0, errL = 0;
-    int nleaf = 0;
-    bool fired = false, hl_defer = false;
-    if (alive)
-      fired = highlight_leaves(S, cur, [&](V3 c) {
-        leafp[3 * nleaf] = c.x;
-        leafp[3 * nleaf + 1] = c.y;
-        leafp[3 * nleaf + 2] = c.z;
-        nleaf++;
-      }, errA, [&](V3, V3, double, int) {         // lit_area's raise: deferred to k_hl_raise
-        hl_defer = true;
-        return false;
-      });
-    lv_hl_defer(p, hl_defer, cur.ray, base + i, [&] { return root; });
-    const bool ext = alive && !fired;
-    double best = S.max_distance, total = 0.0;
-    int besti = -1;
-    V3 hit = v3(0.0, 0.0, 0.0);
-    bool hin = true;
-    if (ext) lv_walk<SPH, BS>(p, lds, true, cur.ray.o, cur.ray.d, hit, 0.0, best, besti, hit, hin, total, errL, XR_NONE);
-    bool shade = ext && besti >= 0;
-    V3 delta = hit, nrm = hit;
-    if (shade) hit_info(S, besti, cur.ray, hit, delta, nrm, hin);
+    LvFirst f;
+    lv_first_half<SPH, BS>(p, lds, level, slot, i, base, depth, active, f, nullptr);
+    bool shade = f.shade;
+    V3 delta = f.hit, nrm = f.hit;
+    // (hit_info alone, not lv_hit_frame: the normal's raises are k_lv_shade's)
+    if (shade) hit_info(S, f.besti, f.cur.ray, f.hit, delta, nrm, f.hin);
     const uint32_t h = lv_wave_alloc(lv_slice_ctr(p.lv_ctl->sh[level], slice), shade ? 1 : 0);
     if (shade && h >= hcap) {                 // the hit queue's slice is full
-      lv_redo(p, root);
+      lv_redo(p, f.root);
       shade = false;
     }
     if (shade) {
-      const V3 qo = vadd(hit, delta);         // the shadow rays' target point (world.rb:76)
+      const V3 hit = f.hit, qo = vadd(hit, delta);   // qo: the shadow rays' target point (world.rb:76)
       double2* q = reinterpret_cast<double2*>(p.lv_hit + (size_t)(((uint32_t)slice << hlog2) + h) * HIT_DOUBLES);
       q[0] = make_double2(hit.x, hit.y);
       q[1] = make_double2(hit.z, qo.x);
       q[2] = make_double2(qo.y, qo.z);
       q[3] = make_double2(
-          __builtin_bit_cast(double, (uint64_t)i | (uint64_t)((uint32_t)besti | (hin ? 0x80000000u : 0u)) << 32),
-          __builtin_bit_cast(double, (uint64_t)slot | (uint64_t)((errA & 0xffu) | (errL & 0xffu) << 8) << 32));
+          __builtin_bit_cast(double, (uint64_t)i | (uint64_t)((uint32_t)f.besti | (f.hin ? 0x80000000u : 0u)) << 32),
+          __builtin_bit_cast(double, (uint64_t)slot | (uint64_t)((f.errA & 0xffu) | (f.errL & 0xffu) << 8) << 32));
     } else if (active) {
-      uint32_t err = errA;
-      if (!err) err = errL;
-      *reinterpret_cast<uint2*>(rec) = make_uint2((err & 0xffu) | ((uint32_t)nleaf << 8), 0u);
+      lv_end_record(f);
     }
   }
 }
@@ -1381,36 +1372,18 @@ __device__ __forceinline__ void k_lv_shade_body(const KParams& p, int level) {
       lv_ray(p, level, (uint32_t)se, cur, root, x, y, sample, valid);
     }
     char* rec = p.lv_rec + (size_t)(base + i) * p.lv_rec_bytes;
-    V3 delta = hit, nrm = hit, nn = hit;
-    double c = 0.0;
-    if (shade) {
-      hit_info(S, besti, cur.ray, hit, delta, nrm, hin);   // the bits k_lv_trace computed
-      nn = vnorm(nrm, errS);                  // n.normalize (world_object.rb:123)
-      c = vcos(cur.ray.d, nrm, errS);         // ray.front.cos(-n): same bits as cos(n)
-    }
+    LvFrame fr;
+    lv_hit_frame(S, shade, besti, cur.ray, hit, hin, fr, errS);   // the bits k_lv_trace computed
     // World#local_lights' areas (k_lv_shadow) into local_lighting's light loop
-    V3 lc = v3(0.0, 0.0, 0.0);
-    int nl = 0;
+    LightSum ls = {v3(0.0, 0.0, 0.0), 0};
     for (int li = 0; li < nL; li++) {
       if (!shade) continue;
       const double2 ar = reinterpret_cast<const double2*>(p.lv_area)[(size_t)hs * nL + li];
       seterr(errL, (uint32_t)__builtin_bit_cast(uint64_t, ar.y));
-      const double tot = ar.x;
-      const double area = tot > 0 ? tot : 0.0;
-      if (area > 0) {
-        const LightDev& L = S.light[li];
-        nl++;
-        const double pw = S.sse_is_two ? area * area : rx_pow(area, S.sse);
-        const V3 lcol = vsc(v3p(L.color), pw / (double)nL);
-        const V3 ll = vnorm(vsub(v3p(L.pos), hit), errP);
-        double ldn = vdot(ll, nn);
-        if (ldn > 1) ldn = 1.0;
-        else if (ldn < 0) ldn = 0.0;
-        lc = vadd(lc, vsc(lcol, ldn));
-      }
+      ls = light_term(S, S.light[li], ar.x, hit, fr.nn, ls.lc, ls.nl, errP);
     }
-    lv_finish(p, level, slice, shade, shade, cur, root, x, y, sample, besti, hin, hit, delta, nrm, nn, c, lc, nl, rec,
-              0, errA, errS, errL, errP, shade ? &S.mat[besti] : S.mat);
+    lv_finish(p, level, slice, shade, shade, cur, root, x, y, sample, besti, hin, hit, fr.delta, fr.nrm, fr.nn, fr.c,
+              ls.lc, ls.nl, rec, 0, errA, errS, errL, errP, shade ? &S.mat[besti] : S.mat);
   }
 }
 

@@ -811,3 +811,144 @@ def test_light_buffer_c2_full_frame_and_options(gpu):
     with pytest.raises(RtxError):
         r.set_option("lbuf", 2)
     assert _same(r.render(), _renderer(sd, cd, 1, lbuf=0).render())
+
+
+# ---- the phases of rt_map that the engines share (rtx_device.h: light_term, leaf_color, sphere_uv, pt_basis / pt_dir)
+SHARED_WORLD = """max_distance: 10000
+soft_shadow_exponent: 2
+lights:
+  - type: Spot
+    properties:
+      name: key
+      position: [4.0, -3.0, 4.0]
+      radius: 0.6
+      color: [0.9, 0.85, 0.8]
+      high_light_rate: 1
+      high_light_angle: 4
+  - type: Spot
+    properties:
+      name: fill
+      position: [1.0, 4.0, 2.0]
+      radius: 0.0
+      color: [0.4, 0.45, 0.5]
+      high_light_rate: 0.5
+      high_light_angle: 2
+world_objects:
+  - type: Sphere
+    properties:
+      name: globe
+      center: [5.0, -2.0, -0.2]
+      radius: 0.8
+      refractive_rate: 1.4
+      diffuse_rate: [0.6, 0.6, 0.6]
+      ambient: [0.02, 0.02, 0.02]
+      reflective_attenuation: [0.15, 0.15, 0.15]
+      refractive_attenuation: [0.0, 0.0, 0.0]
+      north_pole_vec: [0, 0, 1]
+      greenwich_vec: [-1, 0, 0]
+      texture_file_path: %(tex)s/rails_synth.png
+      texture_horizontal_scale: 0.005
+      texture_vertical_scale: 0.005
+      texture_u_offset: 0.1
+      texture_v_offset: 0.2
+  - type: Plane
+    properties:
+      name: ground
+      point: [0, 0, -1]
+      front: [0, 0, 1]
+      up: [1, 0, 0]
+      u_unit: 1
+      v_unit: 1
+      refractive_rate: 1.2
+      diffuse_rate: [0.5, 0.5, 0.5]
+      reflective_attenuation: [0.2, 0.2, 0.2]
+      refractive_attenuation: [0.3, 0.3, 0.3]
+      ambient: [0.02, 0.02, 0.02]
+      texture_file_path: %(tex)s/checker.png
+      texture_horizontal_scale: 0.02
+      texture_vertical_scale: 0.02
+  - type: Box
+    properties:
+      name: slab
+      point: [4.0, 0.0, -0.5]
+      front: [1.0, 0.0, 0.0]
+      up: [0.0, 0.0, 1.0]
+      width_front: 2.0
+      width_up: 0.2
+      width_left: 2.0
+      refractive_rate: 1.3
+      diffuse_rate: [0.3, 0.25, 0.2]
+      ambient: [0.02, 0.02, 0.02]
+      reflective_attenuation: [0.2, 0.2, 0.2]
+      refractive_attenuation: [0.3, 0.3, 0.3]
+  - type: Sphere
+    properties:
+      name: glass
+      center: [3.5, 1.9, -0.55]
+      radius: 0.45
+      refractive_rate: 1.5
+      diffuse_rate: [0.05, 0.05, 0.05]
+      ambient: [0.01, 0.01, 0.01]
+      reflective_attenuation: [0.1, 0.1, 0.1]
+      refractive_attenuation: [0.8, 0.8, 0.8]
+"""
+SHARED_CAMERA = """position: [0.0, 0.0, 0.0]
+up: [0.0, 0.0, 1.0]
+front: [1.0, 0.0, 0.0]
+retina_width: 0.016
+retina_height: 0.009
+aperture_radius: 0.0
+image_distance: 0.01714573877962683
+focal_distance: 0.017
+width: 24
+height: 16
+pre_sample_times: 2
+max_sample_times: 2
+variant_threshold: 0.0005
+trace_depth: 3
+monte_carlo_diffusion_times: 2
+"""
+
+
+def test_shared_phases_bit_identical_across_engines(gpu, tmp_path):
+    """A textured sphere, a textured refracting plane, a box, a glass sphere and
+    two lights; the ground under the floating slab is in the shadow of both, so
+    its hits make path-tracing children.  Every level-kernel variant renders
+    the lanes engine's bits, and the first-hit pass's albedo on the textured
+    sphere is the reference's."""
+    from raytracing_rb_amd import config
+    from oracle import rt_ref
+    from test_gpu_first_hit import _bits, expected
+    w, c = tmp_path / "w.yml", tmp_path / "c.yml"
+    w.write_text(SHARED_WORLD % dict(tex=os.path.join(SCENES, "textures")))
+    c.write_text(SHARED_CAMERA)
+    # the reference's rt_map at every pixel's first ray: some hit has no lit light
+    # (path_tracing's children), some textured hit has one (local_lighting's texture leaf)
+    world, cam = rt_ref.load_scene(str(w), str(c))
+    n_pt = n_tex = 0
+    for y in range(cam.height):
+        for x in range(cam.width):
+            ray = cam.lens_func(x, y, 0)
+            if world.high_lights(ray):
+                continue
+            obj, inter, direction, delta, data = world.intersect(ray)
+            if obj is None:
+                continue
+            lit = world.local_lights(inter + delta)
+            n_pt += not lit
+            n_tex += bool(lit) and obj.texture is not None and not isinstance(obj, rt_ref.Box)
+    assert n_pt >= 1 and n_tex >= 1, (n_pt, n_tex)
+
+    sd, cd = config.load_scene(str(w), str(c))
+    lanes = _renderer(sd, cd, 0).render(seed=5)
+    for opts in (dict(), dict(lv_compact=0), dict(lv_compact=2), dict(lv_split=1), dict(bvh=0),
+                 dict(bvh=2, sphere_src=4)):
+        assert _same(_renderer(sd, cd, 1, **opts).render(seed=5), lanes), opts
+
+    exp = expected(str(w), str(c))
+    globe = exp["ids"][..., 0] == exp["kinds"].index("Sphere")      # object 0: the textured sphere
+    assert globe.any() and exp["textured"][0]
+    r = _renderer(sd, cd, 1)
+    alb = r.first_hit()["albedo"]
+    r.close()
+    assert np.array_equal(_bits(alb[globe]), _bits(exp["geom"][..., 7:10][globe]))
