@@ -76,6 +76,11 @@ module RTX
   extern 'int rtx_tile_probe(void*, void*, int)'
   extern 'int rtx_first_hit_device(void*, int, int, int, int, unsigned long long, int, void*, void*, void*)'
   extern 'int rtx_first_hit(void*, int, int, int, int, unsigned long long, int, void*, void*)'
+  # ---- batched World#intersect / #lit_area / #local_lights (scene only, no camera)
+  extern 'int rtx_intersect_device(void*, int, void*, void*, void*, void*)'
+  extern 'int rtx_intersect(void*, int, void*, void*, void*)'
+  extern 'int rtx_lit_area_device(void*, int, void*, void*, void*, void*, void*, void*)'
+  extern 'int rtx_lit_area(void*, int, void*, void*, void*, void*, void*)'
   extern 'int rtx_lpt_plan(void*, int, int, void*, int, void*)'
   extern 'int rtx_device_count()'
   extern 'int rtx_sync(void*, void*)'

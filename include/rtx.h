@@ -25,6 +25,8 @@
  *                          with intersect_parameters' n and get_uv + Texture#color of the hit
  *                                                         src/objects/{sphere,plane,box,texture}.rb
  *   rtx_first_hit_device  (same, device-resident output, async on a HIP stream)
+ *   rtx_intersect         World#intersect(ray), batched   src/world.rb:37-59
+ *   rtx_lit_area          World#lit_area / #local_lights, batched  src/world.rb:62-80
  *   rtx_trace             RayTracer#trace_sync(x, y, ray) src/ray_tracer.rb:16-46
  *   rtx_path_trace        RayTracer#path_trace_sync(x, y, ray) src/ray_tracer.rb:181-289 (dead code there)
  *   rtx_quantize          Camera#array_to_color + canvas.point  src/camera.rb:105,153-156
@@ -262,6 +264,50 @@ rtx_status rtx_first_hit_device(rtx_context* ctx, int32_t x0, int32_t y0, int32_
 /* Host-buffer variant, synchronous. */
 rtx_status rtx_first_hit(rtx_context* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
                          uint64_t seed, int32_t sample, int32_t* ids, double* geom);
+
+/* Batched World queries.  They need an uploaded scene and no
+ * camera.  n == 0 is RTX_OK and touches nothing; RTX_EINVAL for n < 0, a NULL
+ * context, a missing required pointer or no scene uploaded.  The *_device forms
+ * take device memory and are async on hip_stream; the host forms are synchronous
+ * and do not go through rtx_sync.  None of them records a raise in rtx_sync's
+ * state.  A zero-length front, or a target at the light's position, gives
+ * whatever the render's walks give for the same inputs (IEEE arithmetic, no
+ * special case).
+ *
+ * World#intersect (world.rb:37-59) for n explicit rays.  rays[i*6+0..2] = Ray#front
+ * (not normalized), rays[i*6+3..5] = Ray#position, as rtx_trace.
+ * ids: int32[n][3], as rtx_first_hit ({object, direction, data}; miss {-1,-1,-1}).
+ * geom: double[n][13] = rtx_first_hit's ten values {distance, intersection xyz,
+ * n.normalize xyz, albedo rgb} followed by delta xyz (the fourth value
+ * World#intersect returns; local_lights is called with intersection + delta).
+ * Miss: {max_distance, 0 x 12}.  Either output may be NULL, not both. */
+rtx_status rtx_intersect_device(rtx_context* ctx, int32_t n, const double* d_rays,
+                                int32_t* d_ids, double* d_geom, void* hip_stream);
+rtx_status rtx_intersect(rtx_context* ctx, int32_t n, const double* rays, int32_t* ids, double* geom);
+
+/* World#lit_area (world.rb:62-69) / World#local_lights (world.rb:72-80) for n
+ * targets, double[n][3].
+ * lights == NULL: every scene light in order, L = n_lights (local_lights).
+ *   area[i*L+k]  = lit_area(target_i, light_k.position, light_k.radius)
+ *   color[(i*L+k)*3..] = light_k.color * (area**soft_shadow_exponent / n_lights),
+ *                        zeros where area == 0 (the light is not in local_lights' list).
+ *   color may be NULL.
+ * lights != NULL: double[n][4] = one explicit {position xyz, radius} per query,
+ *   L = 1, color must be NULL (RTX_EINVAL otherwise).
+ * area: double[n][L], required.
+ * status: int32[n], may be NULL.  It holds the rtx_status of the first raise of
+ *   query i in light order (RTX_EDOMAIN for cover_area's Math.acos,
+ *   sphere.rb:45-46), 0 if none.  The raising light's entries and all later
+ *   entries of that query are quiet NaN.  Earlier entries are valid.
+ * Every cover's raise is checked under the option "exact_raises" (the default),
+ * as in a render's shadow walks.
+ * The device call returns RTX_OK whatever the statuses hold.  The host call
+ * returns the status of the first raising query by index (RTX_OK if none) and
+ * names that index in rtx_last_error.  The buffers are filled either way. */
+rtx_status rtx_lit_area_device(rtx_context* ctx, int32_t n, const double* d_targets, const double* d_lights,
+                               double* d_area, double* d_color, int32_t* d_status, void* hip_stream);
+rtx_status rtx_lit_area(rtx_context* ctx, int32_t n, const double* targets, const double* lights,
+                        double* area, double* color, int32_t* status);
 
 /* Longest-processing-time split of n_tiles tiles (costs[t]) over nranks:
  * tiles by decreasing cost (ties: lower index), each to the rank with the

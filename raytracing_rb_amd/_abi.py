@@ -92,6 +92,10 @@ SIGNATURES = [
     ("rtx_tile_probe", _I, [_P, C.POINTER(C.c_int64), _I]),
     ("rtx_first_hit_device", _I, [_P, _I, _I, _I, _I, _U64, _I, _P, _P, _P]),
     ("rtx_first_hit", _I, [_P, _I, _I, _I, _I, _U64, _I, C.POINTER(C.c_int32), _DP]),
+    ("rtx_intersect_device", _I, [_P, _I, _P, _P, _P, _P]),
+    ("rtx_intersect", _I, [_P, _I, _DP, C.POINTER(C.c_int32), _DP]),
+    ("rtx_lit_area_device", _I, [_P, _I, _P, _P, _P, _P, _P, _P]),
+    ("rtx_lit_area", _I, [_P, _I, _DP, _DP, _DP, _DP, C.POINTER(C.c_int32)]),
     ("rtx_lpt_plan", _I, [C.POINTER(C.c_int64), _I, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32)]),
     ("rtx_device_count", _I, []),
     ("rtx_sync", _I, [_P, _P]),

@@ -49,6 +49,38 @@ class World:
         self.soft_shadow_exponent = self.cfg.get("soft_shadow_exponent")
         self.world_objects = self.cfg.get("world_objects") or []
         self.lights = self.cfg.get("lights") or []
+        self._renderer = None                                # the Renderer of the latest Camera made for this world
+
+    # The queries below run on the device scene a Camera of this world uploaded
+    # (one upload per Camera, none here).
+    def _queries(self):
+        if self._renderer is None:
+            raise RuntimeError("World queries need a Camera made for this world (it uploads the scene)")
+        return self._renderer
+
+    def intersect(self, ray):
+        """World#intersect (world.rb:37-59): (index into world_objects or None,
+        intersection, "in" / "out", delta, data) -- Nones on a miss; data is the box
+        face, else None."""
+        g = self._queries().intersect([ray.front.to_a() + ray.position.to_a()])
+        if g["object"][0] < 0:
+            return None, None, None, None, None
+        data = int(g["data"][0])
+        return (int(g["object"][0]), Vec3(*g["position"][0]), "in" if g["direction"][0] == 0 else "out",
+                Vec3(*g["delta"][0]), data if data >= 0 else None)
+
+    def lit_area(self, target, light_pos, radius):
+        """World#lit_area (world.rb:62-69); RtxError(kind "domain") where cover_area's Math.acos raises."""
+        t = target.to_a() if isinstance(target, Vec3) else list(target)
+        lp = light_pos.to_a() if isinstance(light_pos, Vec3) else list(light_pos)
+        area, _, _ = self._queries().lit_area([t], lights=[lp + [float(radius)]])
+        return float(area[0, 0])
+
+    def local_lights(self, position):
+        """World#local_lights (world.rb:72-80): [(index into lights, Vec3 colour)] of the lights with area > 0."""
+        t = position.to_a() if isinstance(position, Vec3) else list(position)
+        area, color, _ = self._queries().lit_area([t])
+        return [(k, Vec3(*color[0, k])) for k in range(area.shape[1]) if area[0, k] > 0]
 
 
 class RayTracer:
@@ -90,6 +122,7 @@ class Camera:
         self.seed = seed
         self.device = device
         self._r = Renderer(world.scene, self.desc, device=device)
+        world._renderer = self._r                            # serves World#intersect / #lit_area / #local_lights
         self.ray_tracer = RayTracer(self._r, seed)
         self.canvas = None                                   # RGBA8 [H, W, 4] once rendered
 

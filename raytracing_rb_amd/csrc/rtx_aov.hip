@@ -14,7 +14,12 @@
 // A miss is {-1, -1, -1} and {max_distance, 0 ...}.  Highlights are not
 // consulted and nothing is raised: the walk's error word is dropped.
 //
-// One pixel per lane, one wave per 8x8 pixel tile (lane l = pixel (l & 7,
+// k_intersect answers the same question for explicit rays (rtx_intersect,
+// DESIGN.md "Batched World queries"): one ray per lane, consecutive rays in
+// consecutive lanes, 13-value records whose last three are the `delta`
+// World#intersect returns.
+//
+// k_first_hit: one pixel per lane, one wave per 8x8 pixel tile (lane l = pixel (l & 7,
 // l >> 3) of the tile), four tiles side by side per 256-thread workgroup: the
 // 64 rays of a wave start together, and the 8 lanes of a tile row (the 32 of a
 // workgroup row) store contiguous records.  Every value is computed by the
@@ -26,17 +31,15 @@ namespace rtx {
 
 constexpr int FH_BS = 256;
 
-// The record of pixel (px_, row) of the region.  SPH: SPH_LIN_SCALAR (ordered
-// linear walk), SPH_BVH_LDS (hierarchy nodes and leaf records staged in LDS) or
+// Record idx of World#intersect(ray).  SPH: SPH_LIN_SCALAR (ordered linear
+// walk), SPH_BVH_LDS (hierarchy nodes and leaf records staged in LDS) or
 // SPH_BVH_GLOBAL (read from global memory); the hierarchy walks keep their
-// per-lane traversal stacks in LDS (p.lds_stack).
-template <int SPH>
-__device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int sample, int px_, int row,
-                                                int32_t* __restrict__ ids, double* __restrict__ geom) {
+// per-lane traversal stacks in LDS (p.lds_stack).  NG: doubles per geom record,
+// 10 (k_first_hit) or 13 (k_intersect: delta appended).
+template <int SPH, int NG>
+__device__ __forceinline__ void first_hit_ray(const KParams& p, char* lds, const Ray& ray, size_t idx,
+                                              int32_t* __restrict__ ids, double* __restrict__ geom) {
   const SceneDev& S = p.scene;                  // kernel argument: scalar loads
-  const CameraDev& cam = *p.cam;
-  const int x = p.x0 + px_, y = p.y0 + row;
-  const Ray ray = lens_ray(cam, lens_target(cam, x, y), x, y, sample, p.seed);
 
   double best = S.max_distance, total = 0.0;
   int besti = -1;
@@ -61,10 +64,10 @@ __device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int
   }
 
   int dir = -1, data = -1;
-  V3 nn = v3(0.0, 0.0, 0.0), alb = nn;
+  V3 nn = v3(0.0, 0.0, 0.0), alb = nn, delta = nn;
   if (besti >= 0) {
     const Material& m = S.mat[besti];
-    V3 delta, n;
+    V3 n;
     hit_info(S, besti, ray, hit, delta, n, hin);          // (boxes: re-evaluates the hit)
     const double* plane = nullptr;                        // the plane, or the box face, hit
     if (m.type == OBJ_SPHERE) {
@@ -99,7 +102,6 @@ __device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int
     }
   }                                                       // (a miss: best is still max_distance, hit zeros)
 
-  const size_t idx = (size_t)row * (size_t)p.nx + (size_t)px_;
   if (ids) {
     int32_t* o = ids + idx * 3;
     o[0] = besti;
@@ -107,20 +109,61 @@ __device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int
     o[2] = data;
   }
   if (geom) {
-    double* g = geom + idx * 10;                          // 80-byte records
-    if ((reinterpret_cast<uintptr_t>(geom) & 15) == 0) {
+    double* g = geom + idx * NG;                          // 80-byte (104-byte) records
+    // (13 doubles: in a 16-byte aligned buffer the odd records start 8 bytes off.  Those store the depth
+    // alone and pairs after it, the even ones pairs and delta z alone; the scalar stores serve a buffer
+    // that is only 8-byte aligned.)
+    const bool al = (reinterpret_cast<uintptr_t>(geom) & 15) == 0;
+    if (al && (NG == 10 || !(idx & 1))) {
       double2* g2 = reinterpret_cast<double2*>(g);
       g2[0] = make_double2(best, hit.x);
       g2[1] = make_double2(hit.y, hit.z);
       g2[2] = make_double2(nn.x, nn.y);
       g2[3] = make_double2(nn.z, alb.x);
       g2[4] = make_double2(alb.y, alb.z);
+      if (NG == 13) {
+        g2[5] = make_double2(delta.x, delta.y);
+        g[12] = delta.z;
+      }
+    } else if (NG == 13 && al) {
+      double2* g2 = reinterpret_cast<double2*>(g + 1);
+      g[0] = best;
+      g2[0] = make_double2(hit.x, hit.y);
+      g2[1] = make_double2(hit.z, nn.x);
+      g2[2] = make_double2(nn.y, nn.z);
+      g2[3] = make_double2(alb.x, alb.y);
+      g2[4] = make_double2(alb.z, delta.x);
+      g2[5] = make_double2(delta.y, delta.z);
     } else {
       g[0] = best;
       g[1] = hit.x, g[2] = hit.y, g[3] = hit.z;
       g[4] = nn.x, g[5] = nn.y, g[6] = nn.z;
       g[7] = alb.x, g[8] = alb.y, g[9] = alb.z;
+      if (NG == 13) g[10] = delta.x, g[11] = delta.y, g[12] = delta.z;
     }
+  }
+}
+
+// The lens wrapper: the record of pixel (px_, row) of the region, its ray Camera#lens_func's.
+template <int SPH>
+__device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int sample, int px_, int row,
+                                                int32_t* __restrict__ ids, double* __restrict__ geom) {
+  const CameraDev& cam = *p.cam;
+  const int x = p.x0 + px_, y = p.y0 + row;
+  const Ray ray = lens_ray(cam, lens_target(cam, x, y), x, y, sample, p.seed);
+  first_hit_ray<SPH, 10>(p, lds, ray, (size_t)row * (size_t)p.nx + (size_t)px_, ids, geom);
+}
+
+// SPH_BVH_LDS: the workgroup's copy of the hierarchy's nodes and leaf records (the only barrier).
+template <int SPH>
+__device__ __forceinline__ void fh_stage(const KParams& p, float4* lds4) {
+  const SceneDev& S = p.scene;
+  if (SPH == SPH_BVH_LDS) {
+    const int nn = S.n_nodes * (int)(sizeof(Bvh4Node) / 16);
+    for (int i = threadIdx.x; i < nn; i += FH_BS) lds4[i] = reinterpret_cast<const float4*>(S.bvh)[i];
+    float4* leaf = reinterpret_cast<float4*>(reinterpret_cast<char*>(lds4) + p.lds_leaf);
+    for (int i = threadIdx.x; i < S.n_slots; i += FH_BS) leaf[i] = reinterpret_cast<const float4*>(S.bvh_sph32)[i];
+    __syncthreads();
   }
 }
 
@@ -131,21 +174,29 @@ __device__ __forceinline__ void first_hit_pixel(const KParams& p, char* lds, int
 template <int SPH>
 __global__ __launch_bounds__(FH_BS) void k_first_hit(KParams p, int sample, int32_t* __restrict__ ids,
                                                       double* __restrict__ geom) {
-  const SceneDev& S = p.scene;
   extern __shared__ float4 lds_fh[];
   char* lds = reinterpret_cast<char*>(lds_fh);
-  if (SPH == SPH_BVH_LDS) {
-    const int nn = S.n_nodes * (int)(sizeof(Bvh4Node) / 16);
-    for (int i = threadIdx.x; i < nn; i += FH_BS) lds_fh[i] = reinterpret_cast<const float4*>(S.bvh)[i];
-    float4* leaf = reinterpret_cast<float4*>(lds + p.lds_leaf);
-    for (int i = threadIdx.x; i < S.n_slots; i += FH_BS) leaf[i] = reinterpret_cast<const float4*>(S.bvh_sph32)[i];
-    __syncthreads();                            // (the only barrier)
-  }
+  fh_stage<SPH>(p, lds_fh);
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int px_ = ((int)blockIdx.x * (FH_BS / 64) + wave) * 8 + (lane & 7);
   const int row = (int)blockIdx.y * 8 + (lane >> 3);
   if (px_ >= p.nx || row >= p.nrows) return;
   first_hit_pixel<SPH>(p, lds, sample, px_, row, ids, geom);
+}
+
+// World#intersect for the explicit rays p.rays[0 .. p.nrays) (6 doubles each: front, position, as
+// rtx_trace): ray i in lane i mod 64 of wave i / 64.  A lane past the batch leaves before the walk
+// (the hierarchy walk ballots over the lanes that entered it).
+template <int SPH>
+__global__ __launch_bounds__(FH_BS) void k_intersect(KParams p, int32_t* __restrict__ ids, double* __restrict__ geom) {
+  extern __shared__ float4 lds_fh[];
+  fh_stage<SPH>(p, lds_fh);
+  const size_t i = (size_t)blockIdx.x * FH_BS + threadIdx.x;
+  if (i >= (size_t)p.nrays) return;
+  Ray ray;
+  ray.d = v3p(p.rays + 6 * i);
+  ray.o = v3p(p.rays + 6 * i + 3);
+  first_hit_ray<SPH, 13>(p, reinterpret_cast<char*>(lds_fh), ray, i, ids, geom);
 }
 
 template <int SPH>
@@ -170,10 +221,12 @@ constexpr int FH_WGS_PER_CU = 4;
 // Otherwise they are read from global memory (C4: 101 KB of records would leave
 // one workgroup per CU, each staging them for 256 pixels: 2.15 ms per 3840x2160
 // frame against 0.78 ms from global memory).
-hipError_t launch_first_hit(KParams p, int mode, int32_t sample, int32_t* d_ids, double* d_geom, hipStream_t s) {
-  if (p.nx <= 0 || p.nrows <= 0) return hipSuccess;
+// Returns the walk (SPH_LIN_SCALAR, SPH_BVH_LDS or SPH_BVH_GLOBAL), fills p's LDS layout and `lds`, its bytes.
+static hipError_t fh_layout(KParams& p, int mode, int& sph, size_t& lds) {
   const SceneDev& S = p.scene;
-  if (!sph_is_bvh(mode) || S.bvh_root == BVH_NONE) return launch_fh<SPH_LIN_SCALAR>(p, 0, sample, d_ids, d_geom, s);
+  sph = SPH_LIN_SCALAR;
+  lds = 0;
+  if (!sph_is_bvh(mode) || S.bvh_root == BVH_NONE) return hipSuccess;
   const size_t stacks = (size_t)S.bvh_stack * FH_BS * 4;   // per-lane traversal stacks (no cover lists: EXTEND only)
   const size_t image = (((size_t)S.n_nodes * sizeof(Bvh4Node) + (size_t)S.n_slots * 16 + 15) & ~(size_t)15) + stacks;
   const bool staged = mode != SPH_BVH_GLOBAL && resolve_mode(S, SPH_BVH_LDS) == SPH_BVH_LDS &&
@@ -188,8 +241,34 @@ hipError_t launch_first_hit(KParams p, int mode, int32_t sample, int32_t* d_ids,
   p.lds_stack = (int32_t)off;
   off += stacks;
   if (off > 64 * 1024) return hipErrorInvalidValue;   // (a traversal stack deeper than 64 entries: no hierarchy built here is)
-  return staged ? launch_fh<SPH_BVH_LDS>(p, off, sample, d_ids, d_geom, s)
-                : launch_fh<SPH_BVH_GLOBAL>(p, off, sample, d_ids, d_geom, s);
+  sph = staged ? SPH_BVH_LDS : SPH_BVH_GLOBAL;
+  lds = off;
+  return hipSuccess;
+}
+
+hipError_t launch_first_hit(KParams p, int mode, int32_t sample, int32_t* d_ids, double* d_geom, hipStream_t s) {
+  if (p.nx <= 0 || p.nrows <= 0) return hipSuccess;
+  int sph;
+  size_t lds;
+  const hipError_t e = fh_layout(p, mode, sph, lds);
+  if (e != hipSuccess) return e;
+  return sph == SPH_LIN_SCALAR ? launch_fh<SPH_LIN_SCALAR>(p, lds, sample, d_ids, d_geom, s)
+         : sph == SPH_BVH_LDS  ? launch_fh<SPH_BVH_LDS>(p, lds, sample, d_ids, d_geom, s)
+                               : launch_fh<SPH_BVH_GLOBAL>(p, lds, sample, d_ids, d_geom, s);
+}
+
+// The same walks and the same staging rule for p.nrays explicit rays (p.rays, device memory).
+hipError_t launch_intersect(KParams p, int mode, int32_t* d_ids, double* d_geom, hipStream_t s) {
+  if (p.nrays <= 0) return hipSuccess;
+  int sph;
+  size_t lds;
+  const hipError_t e = fh_layout(p, mode, sph, lds);
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)(((size_t)p.nrays + FH_BS - 1) / FH_BS));
+  if (sph == SPH_LIN_SCALAR) hipLaunchKernelGGL(k_intersect<SPH_LIN_SCALAR>, grid, dim3(FH_BS), lds, s, p, d_ids, d_geom);
+  else if (sph == SPH_BVH_LDS) hipLaunchKernelGGL(k_intersect<SPH_BVH_LDS>, grid, dim3(FH_BS), lds, s, p, d_ids, d_geom);
+  else hipLaunchKernelGGL(k_intersect<SPH_BVH_GLOBAL>, grid, dim3(FH_BS), lds, s, p, d_ids, d_geom);
+  return hipGetLastError();
 }
 
 }  // namespace rtx

@@ -1638,6 +1638,118 @@ rtx_status rtx_first_hit(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int
   return RTX_OK;
 }
 
+// Batched World queries (rtx_aov.hip k_intersect, rtx_query.hip k_lit_area).
+// They need the scene only: prep() would demand a camera the kernels never
+// read.  Nothing is recorded in the device's raise record.
+static rtx_status prep_query(rtx_context* c, KParams& p, int32_t n) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->have_scene) return fail(c, RTX_EINVAL, "no scene uploaded");
+  memset(&p, 0, sizeof p);
+  p.scene = c->scene;
+  p.nrays = n;
+  p.exact_raises = (int32_t)c->opt_exact_raises;
+  return RTX_OK;
+}
+
+rtx_status rtx_intersect_device(rtx_context* c, int32_t n, const double* d_rays, int32_t* d_ids, double* d_geom,
+                                void* stream) {
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative ray count");
+  if (!c->have_scene) return fail(c, RTX_EINVAL, "no scene uploaded");
+  if (n == 0) return RTX_OK;
+  if (!d_rays) return fail(c, RTX_EINVAL, "null rays");
+  if (!d_ids && !d_geom) return fail(c, RTX_EINVAL, "both output buffers are null");
+  KParams p;
+  const rtx_status s = prep_query(c, p, n);
+  if (s) return s;
+  p.rays = d_rays;
+  HIPCHK(c, launch_intersect(p, sph_mode(c), d_ids, d_geom, (hipStream_t)stream));
+  return RTX_OK;
+}
+
+rtx_status rtx_intersect(rtx_context* c, int32_t n, const double* rays, int32_t* ids, double* geom) {
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative ray count");
+  if (!c->have_scene) return fail(c, RTX_EINVAL, "no scene uploaded");
+  if (n == 0) return RTX_OK;
+  if (!rays) return fail(c, RTX_EINVAL, "null rays");
+  if (!ids && !geom) return fail(c, RTX_EINVAL, "both output buffers are null");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t rb = (size_t)n * 6 * sizeof(double);
+  const size_t geom_bytes = geom ? (size_t)n * 13 * sizeof(double) : 0;
+  const size_t ids_bytes = ids ? (size_t)n * 3 * sizeof(int32_t) : 0;
+  rtx_status s = ensure_scratch(c, rb + geom_bytes + ids_bytes);
+  if (s) return s;
+  char* base = reinterpret_cast<char*>(c->d_scratch);
+  double* d_rays = c->d_scratch;
+  double* d_geom = geom ? reinterpret_cast<double*>(base + rb) : nullptr;
+  int32_t* d_ids = ids ? reinterpret_cast<int32_t*>(base + rb + geom_bytes) : nullptr;
+  HIPCHK(c, hipMemcpy(d_rays, rays, rb, hipMemcpyHostToDevice));
+  if ((s = rtx_intersect_device(c, n, d_rays, d_ids, d_geom, nullptr))) return s;
+  // (stream-ordered blocking copies, as rtx_first_hit: no rtx_sync)
+  if (geom) HIPCHK(c, hipMemcpy(geom, d_geom, geom_bytes, hipMemcpyDeviceToHost));
+  if (ids) HIPCHK(c, hipMemcpy(ids, d_ids, ids_bytes, hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+
+// The argument checks the device and the host form of rtx_lit_area share.  *go: there is work.
+static rtx_status lit_area_args(rtx_context* c, int32_t n, const double* targets, const double* lights,
+                                const double* area, const double* color, bool* go) {
+  *go = false;
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative target count");
+  if (!c->have_scene) return fail(c, RTX_EINVAL, "no scene uploaded");
+  if (n == 0) return RTX_OK;
+  if (!targets) return fail(c, RTX_EINVAL, "null targets");
+  if (!area) return fail(c, RTX_EINVAL, "null area buffer");
+  if (lights && color) return fail(c, RTX_EINVAL, "explicit lights have no colour: color must be null");
+  if ((int64_t)n * std::max(1, c->scene.n_light) > INT32_MAX)
+    return fail(c, RTX_EINVAL, "%d targets x %d lights exceed 2^31 entries", n, c->scene.n_light);
+  *go = true;
+  return RTX_OK;
+}
+
+rtx_status rtx_lit_area_device(rtx_context* c, int32_t n, const double* d_targets, const double* d_lights,
+                               double* d_area, double* d_color, int32_t* d_status, void* stream) {
+  bool go;
+  rtx_status s = lit_area_args(c, n, d_targets, d_lights, d_area, d_color, &go);
+  if (s || !go) return s;
+  KParams p;
+  if ((s = prep_query(c, p, n))) return s;
+  HIPCHK(c, launch_lit_area(p, sph_mode(c), d_targets, d_lights, d_area, d_color, d_status, (hipStream_t)stream));
+  return RTX_OK;
+}
+
+rtx_status rtx_lit_area(rtx_context* c, int32_t n, const double* targets, const double* lights, double* area,
+                        double* color, int32_t* status) {
+  bool go;
+  rtx_status s = lit_area_args(c, n, targets, lights, area, color, &go);
+  if (s || !go) return s;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t L = lights ? 1 : (size_t)c->scene.n_light;
+  const size_t tb = (size_t)n * 3 * sizeof(double), lb = lights ? (size_t)n * 4 * sizeof(double) : 0;
+  const size_t ab = (size_t)n * L * sizeof(double), cb = color ? 3 * ab : 0, sb = (size_t)n * sizeof(int32_t);
+  if ((s = ensure_scratch(c, tb + lb + ab + cb + sb))) return s;
+  char* base = reinterpret_cast<char*>(c->d_scratch);
+  double* d_targets = c->d_scratch;
+  double* d_lights = lights ? reinterpret_cast<double*>(base + tb) : nullptr;
+  double* d_area = reinterpret_cast<double*>(base + tb + lb);
+  double* d_color = color ? reinterpret_cast<double*>(base + tb + lb + ab) : nullptr;
+  int32_t* d_status = reinterpret_cast<int32_t*>(base + tb + lb + ab + cb);   // (always: the return value needs it)
+  HIPCHK(c, hipMemcpy(d_targets, targets, tb, hipMemcpyHostToDevice));
+  if (lights) HIPCHK(c, hipMemcpy(d_lights, lights, lb, hipMemcpyHostToDevice));
+  if ((s = rtx_lit_area_device(c, n, d_targets, d_lights, d_area, d_color, d_status, nullptr))) return s;
+  // (stream-ordered blocking copies, as rtx_first_hit: no rtx_sync)
+  std::vector<int32_t> st((size_t)n);
+  HIPCHK(c, hipMemcpy(area, d_area, ab, hipMemcpyDeviceToHost));
+  if (color) HIPCHK(c, hipMemcpy(color, d_color, cb, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(st.data(), d_status, sb, hipMemcpyDeviceToHost));
+  if (status) memcpy(status, st.data(), sb);
+  for (int32_t i = 0; i < n; i++)
+    if (st[i]) return fail(c, (rtx_status)st[i], "%s at query %d", rtx_status_string((rtx_status)st[i]), i);
+  return RTX_OK;
+}
+
 rtx_status rtx_lpt_plan(const int64_t* costs, int32_t n_tiles, int32_t nranks, int32_t* plan, int32_t cap,
                         int32_t* per_rank) {
   if (n_tiles < 0 || nranks < 1 || (n_tiles > 0 && !costs) || !per_rank) return RTX_EINVAL;

@@ -230,5 +230,16 @@ hipError_t launch_tile_probe(KParams p, int32_t* cls, hipStream_t s);
 // either may be null.  mode: SphMode (a hierarchy mode walks the hierarchy,
 // staged in LDS when it fits, else from global memory).
 hipError_t launch_first_hit(KParams p, int mode, int32_t sample, int32_t* d_ids, double* d_geom, hipStream_t s);
+// Batched World queries over p.nrays items; p.cam is unused.
+// World#intersect of the rays p.rays (rtx_aov.hip): d_ids int32[n][3], d_geom
+// double[n][13] (launch_first_hit's ten values, then delta); either may be null.
+hipError_t launch_intersect(KParams p, int mode, int32_t* d_ids, double* d_geom, hipStream_t s);
+// World#lit_area / #local_lights of the targets d_targets [n][3] (rtx_query.hip)
+// against the scene's lights (d_lights null: L = n_light entries per target) or
+// one explicit light {position, radius} each (d_lights [n][4], L = 1): d_area
+// [n][L], d_color [n][L][3] or null, d_status int32[n] or null (the rtx_status
+// of the target's first raise; nothing goes to p.err).
+hipError_t launch_lit_area(KParams p, int mode, const double* d_targets, const double* d_lights, double* d_area,
+                           double* d_color, int32_t* d_status, hipStream_t s);
 
 }  // namespace rtx

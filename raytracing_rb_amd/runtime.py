@@ -120,6 +120,43 @@ class Renderer:
                                            ids.ctypes.data_as(C.POINTER(C.c_int32)), _dp(geom)))
         return split_first_hit(ids, geom)
 
+    def intersect(self, rays):
+        """World#intersect for rays [n, 6] = (front, position) (rtx_intersect): the
+        dict of ``first_hit`` over [n] (``depth`` = ray.distance(intersection)) plus
+        ``delta`` [n, 3], the offset local_lights is called with (intersection + delta)."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = len(rays)
+        ids = np.empty((n, 3), np.int32)
+        geom = np.empty((n, 13), np.float64)
+        self._check(self.lib.rtx_intersect(self.h, n, _dp(rays), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           _dp(geom)))
+        return split_intersect(ids, geom)
+
+    def lit_area(self, targets, lights=None, want_color=True, check=True):
+        """World#lit_area / #local_lights for targets [n, 3] (rtx_lit_area) ->
+        (area [n, L], color [n, L, 3] or None, status int32 [n]).  lights None: the
+        scene's lights in order (L = their number); else [n, 4] = one explicit
+        {position, radius} per target (L = 1, no colour).  status[i] is the rtx_status
+        of target i's first raise in light order (3: cover_area's Math.acos), its
+        entries from that light on NaN.  check=True raises RtxError for the first
+        raising target; check=False returns the statuses."""
+        targets = np.ascontiguousarray(targets, np.float64).reshape(-1, 3)
+        n = len(targets)
+        if lights is not None:
+            lights = np.ascontiguousarray(lights, np.float64).reshape(-1, 4)
+            if len(lights) != n:
+                raise ValueError("one explicit light per target")
+            want_color = False
+        nl = 1 if lights is not None else self._scene.desc.n_lights
+        area = np.empty((n, nl), np.float64)
+        color = np.empty((n, nl, 3), np.float64) if want_color else None
+        status = np.zeros(n, np.int32)
+        st = self.lib.rtx_lit_area(self.h, n, _dp(targets), _dp(lights) if lights is not None else None, _dp(area),
+                                   _dp(color) if want_color else None, status.ctypes.data_as(C.POINTER(C.c_int32)))
+        if st and (check or not status.any()):      # (a status without a raising target: an argument or HIP error)
+            self._check(st)
+        return area, color, status
+
     def count_work(self, seed=1):
         cnt = (C.c_uint64 * RTX_NCOUNT)()
         self._check(self.lib.rtx_count_work(self.h, seed, cnt))
@@ -140,6 +177,20 @@ class Renderer:
         y1 = self.height if y1 is None else y1
         self._check(self.lib.rtx_first_hit_device(self.h, x0, y0, x1, y1, seed, sample, C.c_void_p(d_ids or 0),
                                                   C.c_void_p(d_geom or 0), C.c_void_p(stream or 0)))
+
+    def intersect_device(self, n, d_rays, d_ids, d_geom, stream=None):
+        """rtx_intersect_device: d_rays float64 [n, 6], d_ids int32 [n, 3], d_geom float64
+        [n, 13] (device pointers; one of the outputs may be None).  Records no raise."""
+        self._check(self.lib.rtx_intersect_device(self.h, n, C.c_void_p(d_rays or 0), C.c_void_p(d_ids or 0),
+                                                  C.c_void_p(d_geom or 0), C.c_void_p(stream or 0)))
+
+    def lit_area_device(self, n, d_targets, d_lights, d_area, d_color=None, d_status=None, stream=None):
+        """rtx_lit_area_device: d_targets float64 [n, 3], d_lights None or float64 [n, 4],
+        d_area float64 [n, L], d_color None or float64 [n, L, 3], d_status None or int32 [n]
+        (device pointers).  Raises go to d_status only."""
+        self._check(self.lib.rtx_lit_area_device(self.h, n, C.c_void_p(d_targets or 0), C.c_void_p(d_lights or 0),
+                                                 C.c_void_p(d_area or 0), C.c_void_p(d_color or 0),
+                                                 C.c_void_p(d_status or 0), C.c_void_p(stream or 0)))
 
     def rows_per_rank(self, tile_rows, nranks):
         return self.lib.rtx_tiles_rows_per_rank(self.height, tile_rows, nranks)
@@ -217,6 +268,13 @@ def split_first_hit(ids, geom):
     """The named views of rtx_first_hit's buffers: ids [H, W, 3], geom [H, W, 10]."""
     return {"object": ids[..., 0], "direction": ids[..., 1], "data": ids[..., 2], "depth": geom[..., 0],
             "position": geom[..., 1:4], "normal": geom[..., 4:7], "albedo": geom[..., 7:10]}
+
+
+def split_intersect(ids, geom):
+    """The named views of rtx_intersect's buffers: ids [n, 3], geom [n, 13]."""
+    out = split_first_hit(ids, geom)
+    out["delta"] = geom[..., 10:13]
+    return out
 
 
 def render_multi(renderers, tile_rows=8, seed=1):
