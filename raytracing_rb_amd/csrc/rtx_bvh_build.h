@@ -1,7 +1,7 @@
 // rtx_bvh_build.h — host-only: the four-wide sphere hierarchy builder and
-// the 16-bit leaf records of SPH_BVH_QLDS.
-// Included by rtx_capi.cpp (rtx_scene_upload) and by tools/walk_sim.cpp, the
-// CPU walk simulator, so both see the same trees.  No HIP calls.
+// the 16-bit leaf records of SPH_BVH_QLDS, the light and raise
+// buffers: the builders rtx_scene_build.h chains into the host scene build, which
+// rtx_scene_upload and the host tools share.  No HIP calls.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -519,8 +519,7 @@ enum { RB_B2 = 0, RB_B1 = 1, RB_M = 2, RB_LISTS = 3 };
 
 inline RaiseBuffer build_raise_buffer(const Bvh4Builder& bb, int root, const double (*lpos)[3], const double* lrad,
                                       const double* lfloor, int n_light, int n, size_t max_words,
-                                      std::vector<double>* floors_used = nullptr, bool per_sphere = false,
-                                      int max_doublings = 31) {
+                                      bool per_sphere = false, int max_doublings = 31) {
   RaiseBuffer rb;
   if (n_light <= 0 || root == BVH_NONE || n <= 0) return rb;
   const int cells = 6 * n * n;
@@ -532,7 +531,6 @@ inline RaiseBuffer build_raise_buffer(const Bvh4Builder& bb, int root, const dou
   const double DELTA = 1e-4, PI = CubeCells::PI, QMAX = 254.0 / 16.0;
   const CubeCells cc(n);
   std::vector<std::vector<uint32_t>> per(n_light);
-  if (floors_used) floors_used->assign(n_light, 0.0);
   size_t total = 0;
   auto as = [PI](double x) { return x >= 1.0 ? PI / 2 : (x <= 0.0 ? 0.0 : std::asin(x)); };
   for (int li = 0; li < n_light; li++) {
@@ -712,7 +710,6 @@ inline RaiseBuffer build_raise_buffer(const Bvh4Builder& bb, int root, const dou
       break;
     }
     if (blk.empty()) return RaiseBuffer{};
-    if (floors_used) (*floors_used)[li] = floor_l;
     total += blk.size();
     if (total > max_words) return RaiseBuffer{};
     per[li].swap(blk);
@@ -749,19 +746,13 @@ inline bool gate_open(uint16_t g, int t, float ql) {   // (the device's test, rt
 // A light's floor^2 rounded up and log2 floor^2 (the gate block's header;
 // rtx_device.h raise_qa / raise_rq).  ql = 8 (log2 |d|^2 - log2 floor^2) is
 // 16 log2(l / floor) to float rounding, far inside the 1e-4 slack of the q's.
-inline float raise_floor2(const RaiseBuffer& rb, int li) {
+inline double raise_floor(const RaiseBuffer& rb, int li) {   // (word 0 of the light's block)
   float fl;
   memcpy(&fl, &rb.words[(size_t)rb.stride * li], 4);
-  const double f2 = (double)fl * (double)fl;
-  float r = (float)f2;
-  if ((double)r < f2) r = nextafterf(r, INFINITY);
-  return r;
+  return (double)fl;
 }
-inline float raise_lf2(const RaiseBuffer& rb, int li) {
-  float fl;
-  memcpy(&fl, &rb.words[(size_t)rb.stride * li], 4);
-  return (float)(2.0 * std::log2((double)fl));
-}
+inline float raise_floor2(const RaiseBuffer& rb, int li) { return f32_up(raise_floor(rb, li) * raise_floor(rb, li)); }
+inline float raise_lf2(const RaiseBuffer& rb, int li) { return (float)(2.0 * std::log2(raise_floor(rb, li))); }
 
 inline std::vector<uint16_t> raise_gates(const RaiseBuffer& rb, int n_light) {
   std::vector<uint16_t> g;

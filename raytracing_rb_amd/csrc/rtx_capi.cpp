@@ -1,8 +1,8 @@
 // rtx_capi.cpp — the C-ABI of librtx (include/rtx.h): scene/camera upload,
 // render entry points, Vec3 helpers.  Host code; kernels in rtx_kernels.hip.
 //
-// Scene preparation restates the constructors of the reference
-// (src/world.rb:15-34, src/objects/{sphere,plane,box,texture}.rb,
+// Scene preparation (rtx_scene_build.h) and the camera's restate the
+// constructors of the reference (src/world.rb:15-34, src/objects/*.rb,
 // src/camera.rb:26-34,129-151) with the same operation order, so every
 // constant the device uses has the bits the Ruby code would compute.
 #include <hip/hip_runtime.h>
@@ -10,29 +10,25 @@
 
 #include <math.h>
 
-#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/rtx.h"
 #include "rtx_launch.h"
 #include "rtx_scene.h"
+#include "rtx_scene_build.h"
 #include "rtx_vec3.h"
 
 using namespace rtx;
 
 #ifndef RTX_BVH_SAH
 #define RTX_BVH_SAH 1                         // default hierarchy splits: 1 binned SAH, 0 median
-#endif
-#ifndef RTX_SAH_PUSHES
-#define RTX_SAH_PUSHES 12                     // SAH only while <= this many traversal-stack entries sit above
 #endif
 
 constexpr unsigned RTX_WORK_RING = 256;
@@ -91,8 +87,8 @@ struct rtx_context {
   int64_t opt_lv_streams = 2;        // bounce levels: P = the region's tiles in P interleaved parts on P streams at once
   int64_t opt_lv_ray_bytes = 0;      // bounce levels: staged ray record, 0 auto (80 B when every path fits 32 bits), 80, 96
   int64_t opt_lv_hl_cap = 0;         // bounce levels: deferred highlight-check list entries (0 auto)
-  int64_t opt_exact_raises = 1;      // 1 (default): local_lights' shadow walks also check the acos raises of the covers they skip (§2.4)
-                                     // (C2 +10 %, C4 +108 %, r09c; so not the default)
+  int64_t opt_exact_raises = 1;      // 1 (default): local_lights' shadow walks also check the acos raises of the covers they skip
+                                     // (§0.0: C2 +3.7 %, C4 +10.4 % against 0)
   int64_t opt_lv_sort = -1;          // bounce levels: 1 = levels visited bin by bin (direction octant, origin cell), 0 off,
                                      // -1 auto = on
   int64_t opt_lv_sort_from = 0;      // bounce levels: the first level binned; 0 auto: level 1 above 512 spheres (C4 354 ->
@@ -147,8 +143,6 @@ static void free_scene(rtx_context* c) {
   c->d_bufs.clear();
   c->have_scene = false;
 }
-
-#include "rtx_bvh_build.h"
 
 extern "C" {
 
@@ -442,341 +436,36 @@ rtx_status rtx_set_option(rtx_context* c, const char* key, int64_t value) {
 }
 
 // ------------------------------------------------------------------ scene
-static void put3(std::vector<double>& g, V3 v) {
-  g.push_back(v.x);
-  g.push_back(v.y);
-  g.push_back(v.z);
-}
-static void set3(double* d, V3 v) {
-  d[0] = v.x;
-  d[1] = v.y;
-  d[2] = v.z;
-}
-
-// Plane record (plane.rb:21-23 reinit + get_uv's re-normalizations :82-83).
-static void put_plane(std::vector<double>& g, V3 P, V3 F, V3 U, double uu, double vu, uint32_t& err) {
-  V3 left = vnorm(vcross(F, U), err);
-  put3(g, P);
-  put3(g, F);
-  put3(g, vnorm(left, err));
-  put3(g, vnorm(U, err));
-  g.push_back(uu);
-  g.push_back(vu);
-}
-
+// The scene is built on the host first (rtx_scene_build.h): a rejected
+// description leaves the previous scene in place.  Then every array goes up.
 rtx_status rtx_scene_upload(rtx_context* c, const rtx_scene_desc* sd) {
   if (!c || !sd) return fail(c, RTX_EINVAL, "null argument");
-  if (sd->n_objects < 0 || sd->n_lights < 0 || sd->n_textures < 0)
-    return fail(c, RTX_EINVAL, "negative counts");
-  if (sd->n_lights > 32) return fail(c, RTX_EINVAL, "at most 32 lights are supported");
-  if ((sd->n_objects && !sd->objects) || (sd->n_lights && !sd->lights) || (sd->n_textures && !sd->textures))
-    return fail(c, RTX_EINVAL, "null array with nonzero count");
+  HostScene H;
+  std::string msg;
   hipSetDevice(c->device);
-  uint32_t err = 0;
-  std::vector<Run> runs;
-  std::vector<Material> mat(sd->n_objects);
-  std::vector<Sphere64> sph64;
-  std::vector<float> sph32;
-  std::vector<int32_t> sph_obj;
-  std::vector<double> planes, boxes;
-  float sph_scale = 0.0f;
-  for (int i = 0; i < sd->n_objects; i++) {
-    const rtx_object_desc& o = sd->objects[i];
-    Material& m = mat[i];
-    memset(&m, 0, sizeof m);
-    set3(m.diffuse, v3p(o.diffuse_rate));
-    set3(m.ambient, v3p(o.ambient));
-    set3(m.refl_att, v3p(o.reflective_attenuation));
-    set3(m.refr_att, v3p(o.refractive_attenuation));
-    m.rr = o.refractive_rate;
-    m.has_rr = o.has_refractive_rate != 0;
-    m.tex = o.texture_id;
-    m.hs = o.texture_horizontal_scale;
-    m.vs = o.texture_vertical_scale;
-    m.type = o.type;
-    if (o.texture_id >= sd->n_textures) return fail(c, RTX_EINVAL, "object %d: bad texture id", i);
-    if (o.type != RTX_SPHERE && o.type != RTX_PLANE && o.type != RTX_BOX)
-      return fail(c, RTX_EINVAL, "object %d: unknown type %d", i, o.type);
-    if (runs.empty() || runs.back().type != o.type) {
-      Run r;
-      r.type = o.type;
-      r.obj0 = i;
-      r.count = 0;
-      r.rec0 = o.type == RTX_SPHERE ? (int)sph64.size()
-             : o.type == RTX_PLANE ? (int)(planes.size() / PLANE_GEO) : (int)(boxes.size() / BOX_GEO);
-      runs.push_back(r);
-    }
-    runs.back().count++;
-    if (o.type == RTX_SPHERE) {
-      if (!o.has_refractive_rate) return fail(c, RTX_EINVAL, "object %d: sphere needs refractive_rate", i);
-      m.rec = (int)sph64.size();
-      sph_obj.push_back(i);
-      Sphere64 sp;
-      set3(sp.c, v3p(o.center));
-      sp.r = o.radius;
-      sph64.push_back(sp);
-      // float32 pre-test record {cx, cy, cz, R^2}; scale = max(|C|_1 + R) (exact culls)
-      sph32.push_back((float)o.center[0]);
-      sph32.push_back((float)o.center[1]);
-      sph32.push_back((float)o.center[2]);
-      sph32.push_back((float)(o.radius * o.radius));
-      const double sc = fabs(o.center[0]) + fabs(o.center[1]) + fabs(o.center[2]) + fabs(o.radius);
-      const float scf = (float)(sc * (1.0 + 1e-6));
-      if (scf > sph_scale) sph_scale = scf;
-      m.u_off = o.texture_u_offset;
-      m.v_off = o.texture_v_offset;
-      if (o.texture_id >= 0) {                     // sphere.rb:18, 113-115
-        const V3 north = v3p(o.north_pole_vec), gw = v3p(o.greenwich_vec);
-        set3(m.gw_n, vnorm(gw, err));
-        set3(m.east_n, vnorm(vcross(north, gw), err));
-        set3(m.north_n, vnorm(north, err));
-      }
-    } else if (o.type == RTX_PLANE) {
-      m.rec = (int)(planes.size() / PLANE_GEO);
-      put_plane(planes, v3p(o.point), v3p(o.front), v3p(o.up), o.u_unit, o.v_unit, err);
-    } else {                                         // box.rb:15-73
-      m.rec = (int)(boxes.size() / BOX_GEO);
-      m.tex = -1;                                    // loaded, never used for shading
-      const V3 P = v3p(o.point), F = v3p(o.front), U = v3p(o.up);
-      const double wf = o.width_front, wu = o.width_up, wl = o.width_left;
-      const V3 left = vnorm(vcross(F, U), err);
-      put_plane(boxes, vadd(P, vsc(vsc(U, wu), 0.5)), U, left, wf, wl, err);
-      put_plane(boxes, vsub(P, vsc(vsc(U, wu), 0.5)), vneg(U), left, wf, wl, err);
-      put_plane(boxes, vadd(P, vsc(vsc(F, wf), 0.5)), F, U, wl, wu, err);
-      put_plane(boxes, vsub(P, vsc(vsc(F, wf), 0.5)), vneg(F), U, wl, wu, err);
-      put_plane(boxes, vadd(P, vsc(vsc(left, wl), 0.5)), left, U, wf, wu, err);
-      put_plane(boxes, vsub(P, vsc(vsc(left, wl), 0.5)), vneg(left), U, wf, wu, err);
-    }
-  }
-  if (err) return fail(c, RTX_EZERO_VEC, "zero vector detected while building the scene");
-  if (!std::isfinite(sph_scale)) return fail(c, RTX_EINVAL, "non-finite sphere coordinates");
-  // bounding-ball hierarchy (before the padding records are appended)
-  std::vector<BSph> bs(sph64.size());
-  for (size_t k = 0; k < sph64.size(); k++) {
-    for (int a = 0; a < 3; a++) bs[k].c[a] = sph64[k].c[a];
-    bs[k].r = sph64[k].r;
-    bs[k].rec = (int)k;
-  }
-  // SAH splits unless their tree would not fit the LDS of a hierarchy
-  // workgroup while the median tree does (C4: the SAH tree spills to global
-  // memory and renders 10 % slower; C2: SAH 1.3 % faster).
-  const std::vector<BSph> bs_in = bs;
-  auto bbp = std::make_unique<Bvh4Builder>(Bvh4Builder{bs, sph64, sph32, sph_obj});
-  bbp->sah = c->opt_bvh_sah != 0;
-  int32_t bvh_root = bs.empty() ? BVH_NONE : bbp->build(0, (int)bs.size(), 0);
-  if (bbp->sah && !bs.empty() &&
-      bvh_lds_bytes((int)bbp->nodes.size(), (int)bbp->slot_obj.size(), bbp->stack + 1) > bvh_lds_budget()) {
-    bs = bs_in;
-    auto med = std::make_unique<Bvh4Builder>(Bvh4Builder{bs, sph64, sph32, sph_obj});
-    med->sah = false;
-    const int32_t r = med->build(0, (int)bs.size(), 0);
-    if (bvh_lds_bytes((int)med->nodes.size(), (int)med->slot_obj.size(), med->stack + 1) <= bvh_lds_budget()) {
-      bbp = std::move(med);
-      bvh_root = r;
-    }
-  }
-  const Bvh4Builder& bb = *bbp;
-  const QuantLeaves ql = quantize_leaves(bb, sph_scale);
-  for (int k = 0; k < 16; k++) sph32.push_back(0.0f);   // 4 padding records: group loads stay in bounds
-  std::vector<LightDev> lights(sd->n_lights);
-  for (int i = 0; i < sd->n_lights; i++) {
-    const rtx_light_desc& l = sd->lights[i];
-    LightDev& d = lights[i];
-    memset(&d, 0, sizeof d);
-    set3(d.pos, v3p(l.position));
-    set3(d.color, v3p(l.color));
-    d.radius = l.radius;
-    d.hl_rate = l.high_light_rate;
-    d.hl_angle_rad = l.high_light_angle / 180.0 * 3.141592653589793;   // world.rb:91
-    const double th = d.hl_angle_rad;
-    if (!(th > 0)) {
-      d.hl_mode = 2;                                 // acos(c) >= 0 can never be < th
-    } else if (th < 1e-6 || th > 1.5) {
-      d.hl_mode = 1;
-    } else {
-      const double ct = cos(th), lo = ct - 1e-7, hi = ct + 1e-7;
-      d.hl_mode = (hi >= 1.0 || lo <= 0.0) ? 1 : 0;
-      d.cos_lo2 = lo * lo;
-      d.cos_hi2 = hi * hi;
-    }
-  }
-  std::vector<TexDev> tex(sd->n_textures);
-  std::vector<uint8_t> texels;
-  for (int i = 0; i < sd->n_textures; i++) {
-    const rtx_texture_desc& t = sd->textures[i];
-    if (t.width <= 0 || t.height <= 0 || !t.rgb) return fail(c, RTX_EINVAL, "texture %d: empty", i);
-    tex[i].w = t.width;
-    tex[i].h = t.height;
-    tex[i].off = (int64_t)texels.size();
-    texels.insert(texels.end(), t.rgb, t.rgb + (size_t)t.width * t.height * 3);
-  }
+  const rtx_status st = build_host_scene(sd, c->opt_bvh_sah != 0, H, msg);
+  if (st != RTX_OK) return fail(c, st, "%s", msg.c_str());
   free_scene(c);
-  auto up = [&](const void* src, size_t bytes, void** dst) -> hipError_t {
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 16);
-    if (e != hipSuccess) return e;
-    c->d_bufs.push_back(p);
-    if (bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    *dst = p;
-    return e;
-  };
   SceneDev& S = c->scene;
-  memset(&S, 0, sizeof S);
-  void* ptr;
-  HIPCHK(c, up(runs.data(), runs.size() * sizeof(Run), &ptr));           S.runs = (const Run*)ptr;
-  HIPCHK(c, up(sph64.data(), sph64.size() * sizeof(Sphere64), &ptr));    S.sph64 = (const Sphere64*)ptr;
-  HIPCHK(c, up(sph32.data(), sph32.size() * sizeof(float), &ptr));       S.sph32 = (const float*)ptr;
-  HIPCHK(c, up(planes.data(), planes.size() * sizeof(double), &ptr));    S.planes = (const double*)ptr;
-  HIPCHK(c, up(boxes.data(), boxes.size() * sizeof(double), &ptr));      S.boxes = (const double*)ptr;
-  HIPCHK(c, up(mat.data(), mat.size() * sizeof(Material), &ptr));        S.mat = (const Material*)ptr;
-  HIPCHK(c, up(bb.nodes.data(), bb.nodes.size() * sizeof(Bvh4Node), &ptr)); S.bvh = (const Bvh4Node*)ptr;
-  HIPCHK(c, up(bb.slot32.data(), bb.slot32.size() * sizeof(float), &ptr)); S.bvh_sph32 = (const float*)ptr;
-  HIPCHK(c, up(bb.slot64.data(), bb.slot64.size() * sizeof(Sphere64), &ptr)); S.bvh_sph64 = (const Sphere64*)ptr;
-  HIPCHK(c, up(ql.rec.data(), ql.rec.size() * sizeof(uint32_t), &ptr)); S.bvh_q = (const uint32_t*)ptr;
-  HIPCHK(c, up(bb.slot_obj.data(), bb.slot_obj.size() * sizeof(int32_t), &ptr)); S.bvh_obj = (const int32_t*)ptr;
-  HIPCHK(c, up(sph_obj.data(), sph_obj.size() * sizeof(int32_t), &ptr)); S.sph_obj = (const int32_t*)ptr;
-  HIPCHK(c, up(lights.data(), lights.size() * sizeof(LightDev), &ptr));  S.light = (const LightDev*)ptr;
-  HIPCHK(c, up(tex.data(), tex.size() * sizeof(TexDev), &ptr));          S.tex = (const TexDev*)ptr;
-  HIPCHK(c, up(texels.data(), texels.size(), &ptr));                     S.texels = (const uint8_t*)ptr;
-  S.n_obj = sd->n_objects;
-  S.n_light = sd->n_lights;
-  S.n_sphere = (int)sph64.size();
-  S.n_plane = (int)(planes.size() / PLANE_GEO);
-  S.n_box = (int)(boxes.size() / BOX_GEO);
-  S.n_runs = (int)runs.size();
-  S.n_nodes = (int)bb.nodes.size();
-  S.n_slots = (int)bb.slot_obj.size();
-  S.bvh_root = bvh_root;
-  S.bvh_stack = bb.stack + 1;
-  {                                                  // the light buffer (scenes whose records the level kernels stage)
-    std::vector<double> lp(3 * (size_t)std::max(1, sd->n_lights));
-    for (int i = 0; i < sd->n_lights; i++)
-      for (int a = 0; a < 3; a++) lp[3 * i + a] = lights[i].pos[a];
-    // small scenes: a table for LDS (<= 16 KB); larger ones: a finer one read
-    // from global memory (<= 512 KB, L2-resident; C4: 160 cells per face side,
-    // 251 ms per frame against 253 ms with 128 and 256 ms with 96, r10t)
-#ifndef RTX_LBUF_GLOBAL_N
-#define RTX_LBUF_GLOBAL_N 160
-#endif
-    std::vector<double> lrad(std::max(1, sd->n_lights), 0.0);
-    for (int i = 0; i < sd->n_lights; i++) lrad[i] = lights[i].radius;
-    LightBuffer lb;
-    const bool small = sph64.size() <= 512;
-    if (sd->n_lights > 0 && !sph64.empty())
-      for (int n : small ? std::vector<int>{24, 16, 12, 8} : std::vector<int>{RTX_LBUF_GLOBAL_N, 128, 96, 64, 48, 32, 24}) {
-        lb = build_light_buffer(bb, bvh_root, reinterpret_cast<const double(*)[3]>(lp.data()), sd->n_lights, n,
-                                small ? LBUF_MAX_WORDS : LBUF_MAX_WORDS_GLOBAL, lrad.data());
-        if (lb.n) break;
-      }
-    if (lb.n) {
-      HIPCHK(c, up(lb.words.data(), lb.words.size() * sizeof(uint16_t), &ptr));
-      S.lbuf = (const uint16_t*)ptr;
-      S.lbuf_n = lb.n;
-      S.lbuf_stride = lb.stride;
-      // the raise buffer (exact_raises): its cells nest in the
-      // light buffer's (small scenes: 12 per face side for C2's 24, gates staged
-      // in LDS; larger: 160, as C4's light buffer), read from global memory; each light's floor
-      // is 0.99 of the distance to the nearest object surface (targets of
-      // World#local_lights lie on surfaces; nearer ones walk the hierarchy)
-      std::vector<double> lfloor(std::max(1, sd->n_lights), 0.0);
-      for (int li = 0; li < sd->n_lights; li++) {
-        const double* L = lights[li].pos;
-        double fl = HUGE_VAL;
-        for (int k = 0; k < sd->n_objects; k++) {
-          const rtx_object_desc& o = sd->objects[k];
-          auto dist = [&](const double* p) {
-            return std::sqrt((L[0] - p[0]) * (L[0] - p[0]) + (L[1] - p[1]) * (L[1] - p[1]) + (L[2] - p[2]) * (L[2] - p[2]));
-          };
-          auto norm = [](const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
-          if (o.type == RTX_SPHERE) {
-            fl = std::min(fl, dist(o.center) - std::fabs(o.radius));
-          } else if (o.type == RTX_PLANE) {
-            const double fn = norm(o.front);
-            fl = std::min(fl, std::fabs((L[0] - o.point[0]) * o.front[0] + (L[1] - o.point[1]) * o.front[1] +
-                                        (L[2] - o.point[2]) * o.front[2]) / fn);
-          } else {                                    // a box: within this ball of its point (box.rb:15-73)
-            const double rb = 0.5 * (std::fabs(o.width_front) * (1.0 + norm(o.front)) +
-                                     std::fabs(o.width_up) * (1.0 + norm(o.up)) + 2.0 * std::fabs(o.width_left));
-            fl = std::min(fl, dist(o.point) - rb);
-          }
-        }
-        lfloor[li] = std::isfinite(fl) ? std::max(0.0, 0.99 * fl) : 0.0;
-      }
-      // (the finest nesting resolution up to 12 / 160 cells per face side whose lists fit at the
-      // lights' own floors; only if none does, a coarse one with the floors raised until it fits)
-#ifndef RTX_RBUF_GLOBAL_N
-#define RTX_RBUF_GLOBAL_N 160      // C4: 294.5 / 285.6 / 283.7 ms per frame at 40 / 80 / 160 (r11y; r11ab: 285.4 / 283.2 at 80 / 160; 77 MB)
-#endif
-      RaiseBuffer rb;
-      const int want = small ? 12 : RTX_RBUF_GLOBAL_N;
-      const size_t rb_max = small ? RBUF_MAX_WORDS : RBUF_MAX_WORDS_GLOBAL;
-      int coarse = 0;
-      for (int nc = std::min(want, lb.n); nc >= 1 && !rb.n; nc--) {
-        if (lb.n % nc) continue;
-        coarse = nc;
-        if (nc < 4) break;
-        rb = build_raise_buffer(bb, bvh_root, reinterpret_cast<const double(*)[3]>(lp.data()), lrad.data(),
-                                lfloor.data(), sd->n_lights, nc, rb_max, nullptr, !small, 0);
-      }
-      if (!rb.n && coarse)
-        rb = build_raise_buffer(bb, bvh_root, reinterpret_cast<const double(*)[3]>(lp.data()), lrad.data(),
-                                lfloor.data(), sd->n_lights, coarse, rb_max, nullptr, !small);
-      if (rb.n) {
-        // per light: floor^2 (rounded up) and log2 floor^2 (float bits, 2 words each), 4 words of
-        // padding, a gate word per cell (rtx_device.h raise_qa)
-        const std::vector<uint16_t> g = raise_gates(rb, sd->n_lights);
-        const int cells = 6 * rb.n * rb.n, gs = (8 + cells + 7) & ~7;
-        std::vector<uint16_t> gw((size_t)gs * sd->n_lights, 0);
-        for (int li = 0; li < sd->n_lights; li++) {
-          const float hw[2] = {raise_floor2(rb, li), raise_lf2(rb, li)};
-          memcpy(&gw[(size_t)gs * li], hw, 8);
-          std::copy(g.begin() + (size_t)cells * li, g.begin() + (size_t)cells * (li + 1), gw.begin() + (size_t)gs * li + 8);
-        }
-        HIPCHK(c, up(rb.words.data(), rb.words.size() * sizeof(uint32_t), &ptr));
-        S.rbuf = (const uint32_t*)ptr;
-        HIPCHK(c, up(gw.data(), gw.size() * sizeof(uint16_t), &ptr));
-        S.rgate = (const uint16_t*)ptr;
-        for (int li = 0; li < sd->n_lights; li++) {   // (raise_qa reads them with the light's data)
-          lights[li].raise_f2 = raise_floor2(rb, li);
-          lights[li].raise_lf2 = raise_lf2(rb, li);
-        }
-        HIPCHK(c, hipMemcpy((void*)S.light, lights.data(), lights.size() * sizeof(LightDev), hipMemcpyHostToDevice));
-        S.rbuf_n = rb.n;
-        S.rbuf_stride = rb.stride;
-        S.rgate_stride = gs;
-        S.rbuf_inv_m = (float)rb.n / (float)lb.n;   // (exact enough: (i + 0.5) m' stays 0.5 / m from an integer)
-        S.rbuf_sphere = small ? 0 : 1;              // larger scenes: per-sphere entries (fewer band tests per walk)
-      }
-    }
-  }
-  S.max_distance = sd->max_distance;
-  S.sse = sd->soft_shadow_exponent;
-  S.sph_scale = sph_scale;
-  S.sse_is_two = sd->soft_shadow_exponent == 2.0;     // glibc pow(x, 2.0) == x*x
-  for (int a = 0; a < 3; a++) S.q_org[a] = ql.org[a], S.q_step[a] = ql.step[a];
-  S.q_rstep = ql.rstep;
-  S.q_ok = ql.ok && S.n_nodes <= 32767 && (int64_t)S.n_slots <= 32767;   // references fit int16 stack entries
-  // a decoded center lies within max_err of the true one; a decoded radius within max_err + 2 rstep of R
-  // (ceil to the step, at most one more step: quantize_leaves)
-  S.q_err = (float)((ql.max_err + 2.0 * (double)ql.rstep) * 1.01 + 1e-9 * ql.max_r);
-  {                                                  // the spheres' box, float32, rounded outwards
-    double mn[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, mx[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (const Sphere64& sp : sph64)
-      for (int a = 0; a < 3; a++) {
-        mn[a] = std::min(mn[a], sp.c[a] - fabs(sp.r));
-        mx[a] = std::max(mx[a], sp.c[a] + fabs(sp.r));
-      }
-    for (int a = 0; a < 3; a++) {
-      if (!(mn[a] <= mx[a])) {                       // no spheres: an empty box far away
-        S.root_c[a] = 3e38f;
-        S.root_h[a] = 0.0f;
-        continue;
-      }
-      const float cf = (float)(0.5 * (mn[a] + mx[a]));
-      const double h = std::max(mx[a] - (double)cf, (double)cf - mn[a]);
-      S.root_c[a] = cf;
-      S.root_h[a] = f32_up(h * (1.0 + 1e-9) + 1e-30);
-    }
+  S = H.dev;
+  const Bvh4Builder& bb = *H.bb;
+  const struct { const void* src; size_t bytes; const void** dst; bool built; } arrays[] = {
+#define RTX_ARRAY(v, member, built) {(v).data(), (v).size() * sizeof((v)[0]), (const void**)&S.member, built}
+      RTX_ARRAY(H.runs, runs, true),         RTX_ARRAY(H.sph64, sph64, true),         RTX_ARRAY(H.sph32, sph32, true),
+      RTX_ARRAY(H.planes, planes, true),     RTX_ARRAY(H.boxes, boxes, true),         RTX_ARRAY(H.mat, mat, true),
+      RTX_ARRAY(bb.nodes, bvh, true),        RTX_ARRAY(bb.slot32, bvh_sph32, true),   RTX_ARRAY(bb.slot64, bvh_sph64, true),
+      RTX_ARRAY(H.ql.rec, bvh_q, true),      RTX_ARRAY(bb.slot_obj, bvh_obj, true),   RTX_ARRAY(H.sph_obj, sph_obj, true),
+      RTX_ARRAY(H.lights, light, true),      RTX_ARRAY(H.tex, tex, true),             RTX_ARRAY(H.texels, texels, true),
+      RTX_ARRAY(H.lb.words, lbuf, H.lb.n != 0), RTX_ARRAY(H.rb.words, rbuf, H.rb.n != 0),
+      RTX_ARRAY(H.gates, rgate, H.rb.n != 0)};
+#undef RTX_ARRAY
+  for (const auto& a : arrays) {
+    if (!a.built) continue;                          // (no light or raise buffer: the pointer stays null)
+    void* p = nullptr;
+    HIPCHK(c, hipMalloc(&p, a.bytes ? a.bytes : 16));
+    c->d_bufs.push_back(p);
+    if (a.bytes) HIPCHK(c, hipMemcpy(p, a.src, a.bytes, hipMemcpyHostToDevice));
+    *a.dst = p;
   }
   HIPCHK(c, hipMemcpy(c->d_scene, &S, sizeof S, hipMemcpyHostToDevice));
   c->have_scene = true;

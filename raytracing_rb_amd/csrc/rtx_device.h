@@ -1815,12 +1815,8 @@ __device__ __forceinline__ ItemPos decode_item(const KParams& p, int k) {
 // one 512-thread workgroup per CU (2 waves per SIMD, the register-limited
 // occupancy), next to its stacks and cover lists.
 constexpr size_t LDS_SPHERE_BYTES = 32 * 1024;
-constexpr size_t LDS_TOTAL_BYTES = 160 * 1024;
 constexpr size_t LDS_LIN_BLOCK_BYTES = 76 * 1024;   // two 256-thread workgroups per CU
-#ifndef RTX_BS_BVH
-#define RTX_BS_BVH 512
-#endif
-constexpr int BS_LIN = 256, BS_BVH = RTX_BS_BVH;
+constexpr int BS_LIN = 256;                         // (LDS_TOTAL_BYTES, BS_BVH: rtx_scene.h)
 #ifndef RTX_WPS
 #define RTX_WPS 2            // waves per SIMD the kernels are compiled for (256 VGPRs)
 #endif

@@ -679,12 +679,6 @@ int stack_bucket(int need) {
 }
 
 
-size_t bvh_lds_bytes(int n_nodes, int n_slots, int bvh_stack) {
-  return (size_t)n_nodes * sizeof(Bvh4Node) + (size_t)n_slots * 16 + (size_t)bvh_stack * BS_BVH * 4 +
-         (size_t)COVER_K * BS_BVH * 12 + 64;
-}
-size_t bvh_lds_budget() { return LDS_TOTAL_BYTES; }
-
 int resolve_mode(const SceneDev& S, int mode) {
   if (mode == SPH_BVH_QLDS) {                  // nodes + 16-bit leaf records + 16-bit stacks, when conservative
     const size_t need = (size_t)S.n_nodes * sizeof(Bvh4Node) + (size_t)S.n_slots * 8 +

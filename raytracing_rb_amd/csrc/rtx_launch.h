@@ -212,11 +212,7 @@ hipError_t launch_path_trace(KParams p, hipStream_t s);
 // (SRC_LIST; exits at once when the list is empty).
 hipError_t launch_redo(const KParams& q, int mode, int maxs, int n, hipStream_t s);
 int read_level_stamps(unsigned long long* out, int reset);   // diagnostic builds
-int resolve_mode(const SceneDev& S, int mode);
-// LDS bytes a hierarchy workgroup needs (nodes + leaf records + traversal
-// stacks + cover lists) and the budget SPH_BVH_LDS has.
-size_t bvh_lds_bytes(int n_nodes, int n_slots, int bvh_stack);
-size_t bvh_lds_budget();
+int resolve_mode(const SceneDev& S, int mode);   // (its budget: rtx_scene.h bvh_lds_bytes / bvh_lds_budget)
 hipError_t launch_quantize(const double* rgb, int w, int h, size_t stride, int blend, uint8_t* out,
                            hipStream_t s);
 // Rank-major packed tiles (n ranks x rows_per_rank rows x w x 3) -> frame rows.

@@ -11,9 +11,10 @@
 //   * planes / box faces: binary64 records.
 //   * Material[n_obj], lights, textures — read once per shaded hit.
 // Every derived constant (normalized axes, box faces, ...) is computed on the
-// host with the reference's operation order (rtx_capi.cpp), so the device sees
-// bit-identical values to what the Ruby code recomputes on every call.
+// host with the reference's operation order (rtx_scene_build.h), so the device
+// sees bit-identical values to what the Ruby code recomputes on every call.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rtx {
@@ -39,7 +40,7 @@ struct Sphere64 {
 };
 
 // Four-wide bounding-box hierarchy over the spheres (built on the host,
-// rtx_capi.cpp).  A node holds the float32 axis-aligned boxes of its (up to)
+// rtx_bvh_build.h).  A node holds the float32 axis-aligned boxes of its (up to)
 // four children; every child box contains every sphere below it exactly
 // (bounds rounded outwards), so a float32 slab test of the box dilated by the
 // margin of DESIGN.md §2.1 that misses proves the exact binary64 test of every
@@ -73,6 +74,22 @@ struct Bvh4Node {
   int32_t child[4];
 };
 static_assert(sizeof(Bvh4Node) == 112, "Bvh4Node layout");
+
+// LDS of a hierarchy workgroup: one BS_BVH-thread workgroup per CU owns the
+// whole LDS_TOTAL_BYTES.  bvh_lds_bytes: the nodes, the float32 leaf records,
+// the lanes' traversal stacks and cover lists (SPH_BVH_LDS); the host's
+// hierarchy choice (rtx_scene_build.h build_hierarchy), resolve_mode and
+// lds_layout all read these three constants.
+constexpr size_t LDS_TOTAL_BYTES = 160 * 1024;
+#ifndef RTX_BS_BVH
+#define RTX_BS_BVH 512
+#endif
+constexpr int BS_BVH = RTX_BS_BVH;
+inline size_t bvh_lds_bytes(int n_nodes, int n_slots, int bvh_stack) {
+  return (size_t)n_nodes * sizeof(Bvh4Node) + (size_t)n_slots * 16 + (size_t)bvh_stack * BS_BVH * 4 +
+         (size_t)COVER_K * BS_BVH * 12 + 64;
+}
+inline size_t bvh_lds_budget() { return LDS_TOTAL_BYTES; }
 
 struct Material {
   double diffuse[3];
@@ -147,9 +164,9 @@ struct SceneDev {
   int32_t lbuf_n, lbuf_stride;
   // raise buffer (rtx_bvh_build.h build_raise_buffer; null when
   // not built): per light rbuf_stride words (floor, count, 3 (6 rbuf_n^2 + 1)
-  // offsets, entries); per light rgate_stride 16-bit gate words: the floor
-  // (float bits), 6 words of padding, one word per raise-buffer cell
-  // (raise_gates); lbuf_n is a multiple of rbuf_n
+  // offsets, entries); per light rgate_stride 16-bit gate words: floor^2 and
+  // log2 floor^2 (float bits, 4 words), 4 words of padding, one gate per
+  // raise-buffer cell from word 8 (raise_gates); lbuf_n is a multiple of rbuf_n
   const uint32_t* rbuf;
   const uint16_t* rgate;
   int32_t rbuf_n, rbuf_stride, rgate_stride;

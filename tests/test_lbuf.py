@@ -4,8 +4,10 @@ buffer: every sphere at a tangency where Sphere#cover_area's
 Math.acos can raise (sphere.rb:42-46) is in a leaf of the lists the device
 reads, unless the device walks the hierarchy for that target.
 
-tools/lbuf_check.cpp builds the hierarchy and the light buffer with librtx's
-host builder (rtx_bvh_build.h) and restates query_lbuf's float32 cell lookup;
+tools/lbuf_check.cpp builds the hierarchy and the buffers with librtx's host
+scene build (rtx_scene_build.h; its "upload" mode: the very buffers, gates and
+floors rtx_scene_upload ships for a world) and restates query_lbuf's float32
+cell lookup;
 for random targets it finds, in binary64, every sphere within R of the segment
 from the target to the light (a superset of World#lit_area's covers) and counts
 those whose leaf is missing from the cell.  The GPU tests compare frames with
@@ -25,8 +27,8 @@ def tool(tmp_path_factory):
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
     exe = str(tmp_path_factory.mktemp("lbuf") / "lbuf_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-w", "-o", exe, os.path.join(ROOT, "tools", "lbuf_check.cpp")],
-                   check=True, timeout=300)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-w", "-o", exe, os.path.join(ROOT, "tools", "lbuf_check.cpp"),
+                    "-DLBUF_CHECK_UPLOAD", "-lz", "-lpthread"], check=True, timeout=300)
     return exe
 
 
@@ -34,10 +36,23 @@ def _run(tool, lights, spheres, n, per_light=20000, raise_nc=None):
     text = "".join("light %s\n" % " ".join(repr(float(x)) for x in L) for L in lights)
     text += "".join("%r %r %r %r\n" % tuple(map(float, s)) for s in spheres)
     args = [tool, str(n), str(per_light)] + (["raise", str(raise_nc)] if raise_nc else [])
-    out = subprocess.run(args, input=text, capture_output=True, text=True, timeout=300)
+    return _counts(subprocess.run(args, input=text, capture_output=True, text=True, timeout=300))
+
+
+def _counts(out):
     assert out.returncode in (0, 3), out.stderr
     f = out.stdout.split()
     return dict(zip(f[0::2], map(int, f[1::2]))), out.stderr
+
+
+def _run_upload(tool, world, per_light=20000, raises=False):
+    if world == "c4_world.yml":
+        import sys
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import make_scenes
+        make_scenes.ensure_c4()
+    args = [tool, "upload", os.path.join(SCENES, world), str(per_light)] + (["raise"] if raises else [])
+    return _counts(subprocess.run(args, capture_output=True, text=True, timeout=300))
 
 
 def _scene_spheres(world, camera):
@@ -53,6 +68,13 @@ def _scene_spheres(world, camera):
 def test_scene_light_buffers_hold_every_cover(tool, world, camera, n):
     lights, spheres, _ = _scene_spheres(world, camera)
     r, err = _run(tool, lights, spheres, n)
+    assert r["covers"] > 1000 and r["misses"] == 0, (r, err)
+
+
+@pytest.mark.parametrize("world", ["c2_world.yml", "mix_world.yml", "c4_world.yml"])
+def test_uploaded_light_buffers_hold_every_cover(tool, world):
+    """The light buffer build_host_scene makes for the world: the one rtx_scene_upload ships."""
+    r, err = _run_upload(tool, world)
     assert r["covers"] > 1000 and r["misses"] == 0, (r, err)
 
 
@@ -91,6 +113,15 @@ def test_scene_raise_buffers_hold_every_tangency(tool, world, camera, n, nc):
     assert r["tangencies"] - r["fallbacks"] > 2000 and r["misses"] == 0, (r, err)
 
 
+@pytest.mark.parametrize("world", ["c2_world.yml", "mix_world.yml", "c4_world.yml"])
+def test_uploaded_raise_buffers_hold_every_tangency(tool, world):
+    """The raise buffer, gate blocks, list kind and floors build_host_scene makes for the
+    world (the divisor search at the lights' own floors over spheres, planes and boxes):
+    the ones rtx_scene_upload ships."""
+    r, err = _run_upload(tool, world, per_light=20000, raises=True)
+    assert r["tangencies"] - r["fallbacks"] > 2000 and r["misses"] == 0, (r, err)
+
+
 def test_raise_buffers_random_scenes_and_lights(tool):
     """Random scenes, lights of random radius anywhere, inside, on and just
     outside a sphere; both nested resolutions."""
@@ -124,12 +155,12 @@ def test_raise_buffer_check_has_teeth(tool, tmp_path):
         (d / "tools").mkdir(parents=True)
         (d / "tools" / "lbuf_lookup.h").write_text(
             src.replace("if (!open[t]) continue;", "if (!open[t] || %s) continue;" % drop).replace(
-                '"../raytracing_rb_amd/csrc/rtx_bvh_build.h"', '"%s/raytracing_rb_amd/csrc/rtx_bvh_build.h"' % ROOT))
+                '"../raytracing_rb_amd/', '"%s/raytracing_rb_amd/' % ROOT))
         chk = open(os.path.join(ROOT, "tools", "lbuf_check.cpp")).read().replace(
-            '"../raytracing_rb_amd/csrc/rtx_bvh_build.h"', '"%s/raytracing_rb_amd/csrc/rtx_bvh_build.h"' % ROOT)
+            '"../raytracing_rb_amd/', '"%s/raytracing_rb_amd/' % ROOT)
         (d / "tools" / "lbuf_check.cpp").write_text(chk)
         exe = str(d / "chk")
-        subprocess.run(["g++", "-O2", "-std=c++17", "-w", "-o", exe, str(d / "tools" / "lbuf_check.cpp")],
-                       check=True, timeout=300)
+        subprocess.run(["g++", "-O2", "-std=c++17", "-w", "-o", exe, str(d / "tools" / "lbuf_check.cpp"),
+                        "-lpthread"], check=True, timeout=300)
         r, err = _run(exe, L, spheres, 24, per_light=20000, raise_nc=8)
         assert r["misses"] > 0, (drop, r)

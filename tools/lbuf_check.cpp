@@ -1,25 +1,25 @@
-// Host-only check of the light buffer (tests/test_lbuf.py).
-// stdin: "light x y z" lines, then "x y z r" sphere lines.  Builds the
-// hierarchy as rtx_scene_upload does (binned SAH) and the light buffer
-// (build_light_buffer, cells per face side argv[1]), then for argv[2] random
-// shadow-ray targets T per light (in and around the spheres' box, on and just
-// off the spheres' surfaces, next to the light) finds every sphere within R of
-// the segment [T, L] in binary64 (a superset of the spheres whose cover the
-// reference counts) and checks that its leaf is listed in the cell the device
-// looks up (query_lbuf's float32 arithmetic, restated below).  Prints the
-// number of targets, of covering spheres and of misses (must be 0).
+// Host-only check of the light buffer (tests/test_lbuf.py). stdin: "light x y z"
+// lines, then "x y z r" sphere lines.  Packs the spheres and builds the hierarchy with
+// rtx_scene_upload's own steps (rtx_scene_build.h) and the light buffer (build_light_buffer, cells per
+// face side argv[1]), then for argv[2] random shadow-ray targets T per light (in and around the
+// spheres' box, on and just off the spheres' surfaces, next to the light) finds every sphere within R
+// of the segment [T, L] in binary64 (a superset of the spheres whose cover the reference counts) and
+// checks that its leaf is listed in the cell the device looks up (query_lbuf's float32 arithmetic,
+// restated below).  Prints the number of targets, of covering spheres and of misses (must be 0).
 //
-// Raise mode (argv[3] = "raise", argv[4] = the raise buffer's cells per face
-// side; lights given as "light x y z radius"): builds the raise buffer as
-// rtx_scene_upload does (floor: 0.99 of the nearest sphere surface) and, for
-// argv[2] targets per light, places a random sphere exactly at a tangency of
-// World#lit_area's acos raise (sphere.rb:42: d = |R - r1|, regime A or B, with
-// a random axis through the light), rounds the target to binary64, checks in
-// binary64 that it lies within 1e-9 S of the tangency, and counts those whose
-// leaf is in none of the device's lists (the light buffer's cell, the raise
-// buffer's B2 / B1 / M lists, lbuf_lookup.h shadow_lists) unless the device
-// would walk the hierarchy for that target.  Prints the tangencies tested, the
-// hierarchy fallbacks and the misses (must be 0).
+// Raise mode (argv[3] = "raise", argv[4] = the raise buffer's cells per face side; lights given as
+// "light x y z radius"): builds the raise buffer at upload's floors (raise_floors) and, for argv[2]
+// targets per light, places a random sphere exactly at a tangency of World#lit_area's acos raise
+// (sphere.rb:42: d = |R - r1|, regime A or B, with a random axis through the light), rounds the target
+// to binary64, checks in binary64 that it lies within 1e-9 S of the tangency, and counts those whose
+// leaf is in none of the device's lists (the light buffer's cell, the raise buffer's B2 / B1 / M lists,
+// lbuf_lookup.h shadow_lists) unless the device would walk the hierarchy for that target.  Prints the
+// tangencies tested, the hierarchy fallbacks and the misses (must be 0).
+//
+// Upload mode (argv[1] = "upload", argv[2] = a world YAML, argv[3] = targets per light, argv[4] =
+// "raise" for the raise check): the checks against the very buffers, gate blocks and floors
+// build_host_scene makes for that world, which rtx_scene_upload ships.  Built only with
+// -DLBUF_CHECK_UPLOAD, which takes the CLI's YAML loader in and so needs -lz.
 #include <math.h>
 #include <stdio.h>
 
@@ -27,7 +27,10 @@
 #include <random>
 #include <string>
 
-#include "../raytracing_rb_amd/csrc/rtx_bvh_build.h"
+#ifdef LBUF_CHECK_UPLOAD
+#include "../raytracing_rb_amd/cli/scene_load.hpp"
+#endif
+#include "../raytracing_rb_amd/csrc/rtx_scene_build.h"
 #include "lbuf_lookup.h"
 
 using namespace rtx;
@@ -51,87 +54,46 @@ double seg_dist(const double A[3], const double B[3], const double C[3]) {
   return sqrt(e);
 }
 
-}  // namespace
-
-int raise_main(int n, int per_light, int nc, const std::vector<double>& lp, const std::vector<double>& lr,
-               const std::vector<Sphere64>& s64, Bvh4Builder& bb, int root, const std::vector<int32_t>& leaf_of);
-
-int main(int argc, char** argv) {
-  const int n = argc > 1 ? atoi(argv[1]) : 16;
-  const int per_light = argc > 2 ? atoi(argv[2]) : 100000;
-  const bool raise_mode = argc > 3 && std::string(argv[3]) == "raise";
-  const int nc = argc > 4 ? atoi(argv[4]) : 8;
-  std::vector<double> lp, lr;
-  std::vector<Sphere64> s64;
-  std::vector<float> s32;
-  std::vector<int32_t> obj;
-  std::string tok;
-  while (std::cin >> tok) {
-    if (tok == "light") {
-      double x, y, z, r = 0.0;
-      std::cin >> x >> y >> z;
-      if (raise_mode) std::cin >> r;
-      lp.insert(lp.end(), {x, y, z});
-      lr.push_back(r);
-      continue;
-    }
-    Sphere64 s;
-    s.c[0] = std::stod(tok);
-    std::cin >> s.c[1] >> s.c[2] >> s.r;
-    s64.push_back(s);
-    for (float v : {(float)s.c[0], (float)s.c[1], (float)s.c[2], (float)(s.r * s.r)}) s32.push_back(v);
-    obj.push_back((int)obj.size());
-  }
-  std::vector<BSph> bs(s64.size());
-  for (size_t k = 0; k < s64.size(); k++) {
-    for (int a = 0; a < 3; a++) bs[k].c[a] = s64[k].c[a];
-    bs[k].r = s64[k].r;
-    bs[k].rec = (int)k;
-  }
-  Bvh4Builder bb{bs, s64, s32, obj};
-  bb.sah = true;
-  const int root = bs.empty() ? BVH_NONE : bb.build(0, (int)bs.size(), 0);
-  const int nl = (int)lp.size() / 3;
-  const LightBuffer lb = build_light_buffer(bb, root, reinterpret_cast<const double(*)[3]>(lp.data()), nl, n, 1u << 30,
-                                            raise_mode ? lr.data() : nullptr);
-  if (!lb.n) {
-    printf("no light buffer\n");
-    return 1;
-  }
-  // sphere -> its leaf reference
-  std::vector<int32_t> leaf_of(s64.size(), BVH_NONE);
-  auto note = [&](int32_t ref) {
+// sphere record -> its leaf reference / its slot
+void sphere_places(const HostScene& H, std::vector<int32_t>& leaf_of, std::vector<int32_t>& slot_of) {
+  const Bvh4Builder& bb = *H.bb;
+  std::vector<int32_t> rec_of_obj(H.mat.size(), -1);
+  for (size_t k = 0; k < H.sph_obj.size(); k++) rec_of_obj[(size_t)H.sph_obj[k]] = (int32_t)k;
+  leaf_of.assign(H.sph64.size(), BVH_NONE);
+  slot_of.assign(H.sph64.size(), -1);
+  for (size_t k = 0; k < bb.slot_obj.size(); k++)
+    if (bb.slot_obj[k] >= 0) slot_of[(size_t)rec_of_obj[(size_t)bb.slot_obj[k]]] = (int32_t)k;
+  for (int32_t ref : leaf_refs(bb, H.dev.bvh_root)) {
     const int v = ~ref, slot0 = (v >> 2) * BVH_LEAF, cnt = (v & 3) + 1;
-    for (int u = 0; u < cnt; u++) {
-      const int rec = bb.slot_obj[(size_t)slot0 + u];
-      if (rec >= 0) leaf_of[(size_t)rec] = ref;
-    }
-  };
-  if (root < 0 && root != BVH_NONE) note(root);
-  for (const Bvh4Node& nd : bb.nodes)
-    for (int k = 0; k < 4; k++)
-      if (nd.child[k] < 0 && nd.child[k] != BVH_NONE) note(nd.child[k]);
-  if (raise_mode) return raise_main(n, per_light, nc, lp, lr, s64, bb, root, leaf_of);
+    for (int u = 0; u < cnt; u++)
+      if (bb.slot_obj[(size_t)slot0 + u] >= 0) leaf_of[(size_t)rec_of_obj[(size_t)bb.slot_obj[(size_t)slot0 + u]]] = ref;
+  }
+}
+
+int cover_check(const HostScene& H, int per_light) {
+  const int n = H.lb.n, nl = H.dev.n_light;
+  std::vector<int32_t> leaf_of, slot_of;
+  sphere_places(H, leaf_of, slot_of);
   double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-  for (const Sphere64& s : s64)
+  for (const Sphere64& s : H.sph64)
     for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], s.c[a] - s.r), hi[a] = std::max(hi[a], s.c[a] + s.r);
   std::mt19937_64 rng(12345);
   std::uniform_real_distribution<double> U(0.0, 1.0);
   long targets = 0, covers = 0, misses = 0, listed = 0;
   for (int li = 0; li < nl; li++) {
-    const double* L = &lp[3 * li];
-    const uint16_t* blk = lb.words.data() + (size_t)lb.stride * li;
+    const double* L = &H.lpos[3 * li];
+    const uint16_t* blk = H.lb.words.data() + (size_t)H.lb.stride * li;
     const uint16_t* ent = blk + 6 * n * n + 1;
     for (int k = 0; k < per_light; k++) {
       double T[3];
       const int kind = k % 4;
-      if (kind == 0 || s64.empty()) {                 // the box and around it
+      if (kind == 0 || H.sph64.empty()) {                 // the box and around it
         for (int a = 0; a < 3; a++) {
           const double w = hi[a] - lo[a] + 1.0;
           T[a] = lo[a] - 0.5 * w + 2.0 * w * U(rng);
         }
       } else if (kind <= 2) {                         // on or just off a sphere (shading targets)
-        const Sphere64& s = s64[(size_t)(U(rng) * s64.size()) % s64.size()];
+        const Sphere64& s = H.sph64[(size_t)(U(rng) * H.sph64.size()) % H.sph64.size()];
         double u[3], r2 = 0;
         do {
           r2 = 0;
@@ -148,8 +110,8 @@ int main(int argc, char** argv) {
       if (cell < 0) continue;                         // (the device walks the hierarchy)
       targets++;
       listed += blk[cell + 1] - blk[cell];
-      for (size_t si = 0; si < s64.size(); si++) {
-        if (!(seg_dist(T, L, s64[si].c) <= s64[si].r * (1 + 1e-9))) continue;
+      for (size_t si = 0; si < H.sph64.size(); si++) {
+        if (!(seg_dist(T, L, H.sph64[si].c) <= H.sph64[si].r * (1 + 1e-9))) continue;
         covers++;
         bool found = false;
         for (int e = blk[cell]; e < blk[cell + 1] && !found; e++) found = (int32_t)(int16_t)ent[e] == leaf_of[si];
@@ -161,49 +123,31 @@ int main(int argc, char** argv) {
       }
     }
   }
-  size_t words = 0;
-  for (int li = 0; li < nl; li++) words += lb.stride;
-  printf("n %d targets %ld covers %ld misses %ld words %zu listed_x100 %ld\n", n, targets, covers, misses, words,
-         targets ? 100 * listed / targets : 0);
+  printf("n %d targets %ld covers %ld misses %ld words %zu listed_x100 %ld\n", n, targets, covers, misses,
+         (size_t)H.lb.stride * nl, targets ? 100 * listed / targets : 0);
   return misses ? 3 : 0;
 }
 
 // ------------------------------------------------------------------ raise mode
-int raise_main(int n, int per_light, int nc, const std::vector<double>& lp, const std::vector<double>& lr,
-               const std::vector<Sphere64>& s64, Bvh4Builder& bb, int root, const std::vector<int32_t>& leaf_of) {
-  const int nl = (int)lr.size();
-  std::vector<double> lf(nl);
-  for (int li = 0; li < nl; li++) {
-    double fl = HUGE_VAL;
-    for (const Sphere64& s : s64) {
-      const double w[3] = {s.c[0] - lp[3 * li], s.c[1] - lp[3 * li + 1], s.c[2] - lp[3 * li + 2]};
-      fl = std::min(fl, sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) - s.r);
-    }
-    lf[li] = std::isfinite(fl) ? std::max(0.0, 0.99 * fl) : 0.0;
-  }
-  LightBuffer lb = build_light_buffer(bb, root, reinterpret_cast<const double(*)[3]>(lp.data()), nl, n, 1u << 30,
-                                      lr.data());
-  const bool per_sphere = s64.size() > 512;          // (rtx_scene_upload's choice)
-  RaiseBuffer rb = build_raise_buffer(bb, root, reinterpret_cast<const double(*)[3]>(lp.data()), lr.data(), lf.data(),
-                                      nl, nc, (size_t)1 << 30, nullptr, per_sphere);
-  std::vector<int32_t> slot_of(s64.size(), -1);
-  for (size_t k = 0; k < bb.slot_obj.size(); k++)
-    if (bb.slot_obj[k] >= 0) slot_of[(size_t)bb.slot_obj[k]] = (int32_t)k;
-  if (!lb.n || !rb.n || lb.n % rb.n) {
+int raise_check(const HostScene& H, int per_light) {
+  const int nl = H.dev.n_light;
+  const bool per_sphere = H.dev.rbuf_sphere != 0;
+  if (!H.lb.n || !H.rb.n || H.lb.n % H.rb.n) {
     printf("no buffers\n");
     return 1;
   }
-  const std::vector<uint16_t> gates = raise_gates(rb, nl);
+  std::vector<int32_t> leaf_of, slot_of;
+  sphere_places(H, leaf_of, slot_of);
   std::mt19937_64 rng(777);
   std::uniform_real_distribution<double> U(0.0, 1.0);
   long tested = 0, fallback = 0, misses = 0, listed = 0;
   for (int li = 0; li < nl; li++) {
-    const double* L = &lp[3 * li];
-    const double rad = lr[li];
+    const double* L = &H.lpos[3 * li];
+    const double rad = H.lrad[li];
     if (!(rad > 0.0)) continue;
     for (int k = 0; k < per_light; k++) {
-      const size_t si = (size_t)(U(rng) * s64.size()) % s64.size();
-      const Sphere64& sp = s64[si];
+      const size_t si = (size_t)(U(rng) * H.sph64.size()) % H.sph64.size();
+      const Sphere64& sp = H.sph64[si];
       double u[3], r2;
       do {
         r2 = 0;
@@ -248,10 +192,11 @@ int raise_main(int n, int per_light, int nc, const std::vector<double>& lp, cons
       const double scale = fabs(L[0]) + fabs(L[1]) + fabs(L[2]) + fabs(sp.c[0]) + fabs(sp.c[1]) + fabs(sp.c[2]) + sp.r;
       if (!(fabs(dd1 - fabs(sp.r - r1)) <= 1e-9 * scale) || !(sqrt(ltn2) > 0)) continue;   // (not near a tangency)
       tested++;
-      const lbuf_host::Lists ls = lbuf_host::shadow_lists(lb.words.data() + (size_t)lb.stride * li, lb.n,
-                                                          rb.words.data() + (size_t)rb.stride * li,
-                                                          gates.data() + (size_t)6 * rb.n * rb.n * li, rb.n, lt,
-                                                          raise_floor2(rb, li), raise_lf2(rb, li), per_sphere);
+      // the gate block as the device reads it: the cells' gates from word 8, the floats the light carries
+      const lbuf_host::Lists ls = lbuf_host::shadow_lists(H.lb.words.data() + (size_t)H.lb.stride * li, H.lb.n,
+                                                          H.rb.words.data() + (size_t)H.rb.stride * li,
+                                                          H.gates.data() + (size_t)H.dev.rgate_stride * li + 8, H.rb.n, lt,
+                                                          H.lights[li].raise_f2, H.lights[li].raise_lf2, per_sphere);
       if (ls.fallback) {
         fallback++;
         continue;
@@ -270,7 +215,71 @@ int raise_main(int n, int per_light, int nc, const std::vector<double>& lp, cons
       }
     }
   }
-  printf("n %d nc %d per_sphere %d tangencies %ld fallbacks %ld misses %ld rbuf_words %d listed_x100 %ld\n", n, nc,
-         (int)per_sphere, tested, fallback, misses, rb.stride, tested ? 100 * listed / std::max(1L, tested - fallback) : 0);
+  printf("n %d nc %d per_sphere %d tangencies %ld fallbacks %ld misses %ld rbuf_words %d listed_x100 %ld\n", H.lb.n, H.rb.n,
+         (int)per_sphere, tested, fallback, misses, H.rb.stride, tested ? 100 * listed / std::max(1L, tested - fallback) : 0);
   return misses ? 3 : 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  HostScene H;
+  std::string msg;
+#ifdef LBUF_CHECK_UPLOAD
+  if (argc > 2 && std::string(argv[1]) == "upload") {
+    rtxcli::Scene sc;
+    rtxcli::load_world(argv[2], sc);
+    if (build_host_scene(&sc.desc, true, H, msg) != RTX_OK || !H.lb.n) {
+      printf("no light buffer %s\n", msg.c_str());
+      return 1;
+    }
+    const int per_light = argc > 3 ? atoi(argv[3]) : 20000;
+    return argc > 4 && std::string(argv[4]) == "raise" ? raise_check(H, per_light) : cover_check(H, per_light);
+  }
+#endif
+  const int n = argc > 1 ? atoi(argv[1]) : 16;
+  const int per_light = argc > 2 ? atoi(argv[2]) : 100000;
+  const bool raise_mode = argc > 3 && std::string(argv[3]) == "raise";
+  const int nc = argc > 4 ? atoi(argv[4]) : 8;
+  std::vector<rtx_object_desc> objs;
+  std::vector<rtx_light_desc> lights;
+  std::string tok;
+  while (std::cin >> tok) {
+    if (tok == "light") {
+      rtx_light_desc l{};
+      std::cin >> l.position[0] >> l.position[1] >> l.position[2];
+      if (raise_mode) std::cin >> l.radius;
+      lights.push_back(l);
+      continue;
+    }
+    rtx_object_desc o{};
+    o.type = RTX_SPHERE;
+    o.texture_id = -1;
+    o.has_refractive_rate = 1;
+    o.center[0] = std::stod(tok);
+    std::cin >> o.center[1] >> o.center[2] >> o.radius;
+    objs.push_back(o);
+  }
+  rtx_scene_desc sd{};
+  sd.n_objects = (int32_t)objs.size(), sd.objects = objs.data();
+  sd.n_lights = (int32_t)lights.size(), sd.lights = lights.data();
+  if (pack_objects(&sd, H, msg) != RTX_OK) {
+    printf("bad scene %s\n", msg.c_str());
+    return 1;
+  }
+  build_hierarchy(H, true);
+  pack_lights(&sd, H);
+  H.lb = build_light_buffer(*H.bb, H.dev.bvh_root, H.light_pos(), sd.n_lights, n, 1u << 30,
+                            raise_mode ? H.lrad.data() : nullptr);
+  if (!H.lb.n) {
+    printf("no light buffer\n");
+    return 1;
+  }
+  if (!raise_mode) return cover_check(H, per_light);
+  H.lfloor = raise_floors(&sd);
+  H.dev.rbuf_sphere = small_scene(H) ? 0 : 1;          // (rtx_scene_upload's choice)
+  H.rb = build_raise_buffer(*H.bb, H.dev.bvh_root, H.light_pos(), H.lrad.data(), H.lfloor.data(), sd.n_lights, nc,
+                            (size_t)1 << 30, H.dev.rbuf_sphere != 0);
+  pack_gates(H);
+  return raise_check(H, per_light);
 }

@@ -1,0 +1,56 @@
+// scene_dump.cpp — prints what rtx_scene_upload would send for a world YAML
+// (tests/test_scene_build.py).  Runs build_host_scene (rtx_scene_build.h) and
+// prints one line per device array, "array <name> <bytes> <64-bit FNV-1a>",
+// then the scalars of SceneDev, "scalar <name> <value>" (floats as %a).
+// Host code only, no GPU call.
+//
+//   g++ -O2 -std=c++17 -ffp-contract=off -o scene_dump tools/scene_dump.cpp -lz -lpthread
+//   scene_dump scenes/c2_world.yml [sah: 1 (default) or 0]
+#include <stdio.h>
+
+#include "../raytracing_rb_amd/cli/scene_load.hpp"
+#include "../raytracing_rb_amd/csrc/rtx_scene_build.h"
+
+using namespace rtx;
+
+static uint64_t fnv1a(const void* p, size_t n) {
+  uint64_t h = 1469598103934665603ull;
+  const unsigned char* b = (const unsigned char*)p;
+  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
+  return h;
+}
+
+template <typename T>
+static void array(const char* name, const std::vector<T>& v) {
+  printf("array %s %zu %016llx\n", name, v.size() * sizeof(T), (unsigned long long)fnv1a(v.data(), v.size() * sizeof(T)));
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) {
+    fprintf(stderr, "usage: %s world.yml [sah]\n", argv[0]);
+    return 2;
+  }
+  rtxcli::Scene sc;
+  rtxcli::load_world(argv[1], sc);
+  HostScene H;
+  std::string msg;
+  const rtx_status st = build_host_scene(&sc.desc, argc < 3 || argv[2][0] != '0', H, msg);
+  if (st != RTX_OK) {
+    printf("status %d %s\n", (int)st, msg.c_str());
+    return 1;
+  }
+  array("runs", H.runs), array("sph64", H.sph64), array("sph32", H.sph32), array("planes", H.planes);
+  array("boxes", H.boxes), array("mat", H.mat), array("bvh", H.bb->nodes), array("bvh_sph32", H.bb->slot32);
+  array("bvh_sph64", H.bb->slot64), array("bvh_q", H.ql.rec), array("bvh_obj", H.bb->slot_obj);
+  array("sph_obj", H.sph_obj), array("light", H.lights), array("tex", H.tex), array("texels", H.texels);
+  array("lbuf", H.lb.words), array("rbuf", H.rb.words), array("rgate", H.gates);
+  const SceneDev& S = H.dev;
+#define I(f) printf("scalar " #f " %d\n", (int)S.f)
+#define F(f) printf("scalar " #f " %a\n", (double)S.f)
+  I(n_obj), I(n_light), I(n_sphere), I(n_plane), I(n_box), I(n_runs), I(n_nodes), I(n_slots), I(bvh_root), I(bvh_stack);
+  F(max_distance), F(sse), F(sph_scale), I(sse_is_two);
+  F(q_org[0]), F(q_org[1]), F(q_org[2]), F(q_step[0]), F(q_step[1]), F(q_step[2]), F(q_rstep), I(q_ok), F(q_err);
+  F(root_c[0]), F(root_c[1]), F(root_c[2]), F(root_h[0]), F(root_h[1]), F(root_h[2]);
+  I(lbuf_n), I(lbuf_stride), I(rbuf_n), I(rbuf_stride), I(rgate_stride), I(rbuf_sphere), F(rbuf_inv_m);
+  return 0;
+}

@@ -1,7 +1,7 @@
 // walk_sim.cpp — CPU simulator of librtx's hierarchy walks (analysis tool; not
 // product code, not the oracle).  It loads a scene with the native CLI's YAML
-// loader, builds the hierarchy with the library's own host builder
-// (csrc/rtx_bvh_build.h), traces a sample of the camera's ray trees in binary64
+// loader, builds the scene with the library's own host scene build (csrc/rtx_scene_build.h: the
+// records, tree, buffers and floors of rtx_scene_upload), traces the camera's ray trees in binary64
 // (approximate shading: the ray distribution, not the pixels, is what matters
 // here) and, for every shadow ray of World#local_lights, counts the work of the
 // shadow walk under several culling rules:
@@ -31,74 +31,32 @@
 #include <vector>
 
 #include "../raytracing_rb_amd/cli/scene_load.hpp"
-#include "../raytracing_rb_amd/csrc/rtx_bvh_build.h"
-#include "../raytracing_rb_amd/csrc/rtx_vec3.h"
+#include "../raytracing_rb_amd/csrc/rtx_scene_build.h"
 #include "lbuf_lookup.h"
 
 using namespace rtx;
 
 namespace {
 
-size_t lds_bytes(int n_nodes, int n_slots, int stack) {   // rtx_kernels.hip bvh_lds_bytes
-  return (size_t)n_nodes * sizeof(Bvh4Node) + (size_t)n_slots * 16 + (size_t)stack * 512 * 4 + 4 * 512 * 12 + 64;
-}
-
-struct Sim {
+// The scene as rtx_scene_upload builds it, plus the description's objects and lights (binary64 geometry).
+struct Sim : HostScene {
   std::vector<rtx_object_desc> obj;
-  std::vector<rtx_light_desc> lights;
-  std::vector<Sphere64> sph64;
-  std::vector<float> sph32;
-  std::vector<int32_t> sph_obj;
-  Bvh4Builder* bb = nullptr;
-  int root = BVH_NONE;
-  float sph_scale = 0.0f;
-  float root_c[3], root_h[3];
-  float q_err = 0.0f;
+  std::vector<rtx_light_desc> lights;   // (hides HostScene::lights, the device records)
   bool q16 = false;
   double maxd = 1e4;
 
-  void build(bool sah) {
-    for (size_t i = 0; i < obj.size(); i++) {
-      const rtx_object_desc& o = obj[i];
-      if (o.type != RTX_SPHERE) continue;
-      Sphere64 s;
-      for (int a = 0; a < 3; a++) s.c[a] = o.center[a];
-      s.r = o.radius;
-      sph64.push_back(s);
-      sph_obj.push_back((int)i);
-      for (int a = 0; a < 3; a++) sph32.push_back((float)o.center[a]);
-      sph32.push_back((float)(o.radius * o.radius));
-      const float sc = (float)((fabs(o.center[0]) + fabs(o.center[1]) + fabs(o.center[2]) + fabs(o.radius)) * (1 + 1e-6));
-      sph_scale = std::max(sph_scale, sc);
+  void build(const rtx_scene_desc& sd, bool sah) {
+    obj.assign(sd.objects, sd.objects + sd.n_objects);
+    lights.assign(sd.lights, sd.lights + sd.n_lights);
+    maxd = sd.max_distance;
+    std::string msg;
+    if (pack_objects(&sd, *this, msg) != RTX_OK) {
+      fprintf(stderr, "%s\n", msg.c_str());
+      exit(1);
     }
-    std::vector<BSph>* bs = new std::vector<BSph>(sph64.size());
-    for (size_t k = 0; k < sph64.size(); k++) {
-      for (int a = 0; a < 3; a++) (*bs)[k].c[a] = sph64[k].c[a];
-      (*bs)[k].r = sph64[k].r;
-      (*bs)[k].rec = (int)k;
-    }
-    const std::vector<BSph> in = *bs;
-    bb = new Bvh4Builder{*bs, sph64, sph32, sph_obj};
-    bb->sah = sah;
-    root = bs->empty() ? BVH_NONE : bb->build(0, (int)bs->size(), 0);
-    // (the library's rule: the median tree when only it fits LDS; WAVE_SIM_TREE=sah keeps the SAH tree)
+    // (the library's rule: the median tree when only it fits LDS; WAVE_SIM_TREE=median / sah forces one)
     const char* force = getenv("WAVE_SIM_TREE");
-    if (force && !strcmp(force, "median") && sah) {
-      *bs = in;
-      bb = new Bvh4Builder{*bs, sph64, sph32, sph_obj};
-      bb->sah = false;
-      root = bs->empty() ? BVH_NONE : bb->build(0, (int)bs->size(), 0);
-    }
-    if (sah && !force && lds_bytes((int)bb->nodes.size(), (int)bb->slot_obj.size(), bb->stack + 1) > 160 * 1024) {
-      std::vector<BSph>* b2 = new std::vector<BSph>(in);
-      Bvh4Builder* med = new Bvh4Builder{*b2, sph64, sph32, sph_obj};
-      med->sah = false;
-      const int r = med->build(0, (int)b2->size(), 0);
-      if (lds_bytes((int)med->nodes.size(), (int)med->slot_obj.size(), med->stack + 1) <= 160 * 1024) {
-        bb = med;
-        root = r;
-      }
-    }
+    build_hierarchy(*this, sah && !(force && !strcmp(force, "median")), !force);
     if (const char* qb = getenv("WAVE_SIM_QUANT")) {   // child boxes on an 2^bits grid over the node's own box, rounded out
       const float steps = (float)((1 << atoi(qb)) - 1);
       for (Bvh4Node& n : bb->nodes)
@@ -115,16 +73,9 @@ struct Sim {
           }
         }
     }
-    const QuantLeaves ql = quantize_leaves(*bb, sph_scale);
+    pack_quantized_leaves(*this);
     q16 = ql.ok && sph64.size() > 256;        // C4-sized scenes run SPH_BVH_QLDS
-    q_err = (float)((ql.max_err + 2.0 * (double)ql.rstep) * 1.01 + 1e-9 * ql.max_r);
-    double mn[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, mx[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (const Sphere64& s : sph64)
-      for (int a = 0; a < 3; a++) mn[a] = std::min(mn[a], s.c[a] - s.r), mx[a] = std::max(mx[a], s.c[a] + s.r);
-    for (int a = 0; a < 3; a++) {
-      root_c[a] = (float)(0.5 * (mn[a] + mx[a]));
-      root_h[a] = (float)(std::max(mx[a] - root_c[a], root_c[a] - mn[a]) * (1 + 1e-6));
-    }
+    sphere_box(*this);
   }
 };
 
@@ -175,7 +126,7 @@ RayF rayf(const Sim& S, V3 o, V3 d) {
   r.o[0] = (float)o.x, r.o[1] = (float)o.y, r.o[2] = (float)o.z;
   r.d[0] = (float)d.x, r.d[1] = (float)d.y, r.d[2] = (float)d.z;
   r.dd = r.d[0] * r.d[0] + r.d[1] * r.d[1] + r.d[2] * r.d[2];
-  r.Sx = fabsf(r.o[0]) + fabsf(r.o[1]) + fabsf(r.o[2]) + S.sph_scale;
+  r.Sx = fabsf(r.o[0]) + fabsf(r.o[1]) + fabsf(r.o[2]) + S.dev.sph_scale;
   r.mS = CULL_M * r.Sx;
   const float l1 = fabsf(r.d[0]) + fabsf(r.d[1]) + fabsf(r.d[2]), tiny = 1e-20f * l1;
   for (int a = 0; a < 3; a++) {
@@ -224,8 +175,8 @@ void nappe_bounds(const Sim& S, const RayF& r, float rad, float mg, float& tb, f
   for (int a = 0; a < 3; a++) {
     const float ad = fabsf(r.d[a]), den = ad - rad;
     if (!(den > 1e-5f * (ad + rad))) continue;
-    const float lo = S.root_c[a] - S.root_h[a], hi = S.root_c[a] + S.root_h[a];
-    tm = fminf(tm, (S.root_h[a] + mg + fabsf(S.root_c[a] - r.o[a])) / den);
+    const float lo = S.dev.root_c[a] - S.dev.root_h[a], hi = S.dev.root_c[a] + S.dev.root_h[a];
+    tm = fminf(tm, (S.dev.root_h[a] + mg + fabsf(S.dev.root_c[a] - r.o[a])) / den);
     const float up = (hi + mg - r.o[a]) / den, dn = (r.o[a] - lo + mg) / den;   // toward +a / -a
     if (r.d[a] > 0) tf = fminf(tf, up), tb = fminf(tb, dn);
     else tf = fminf(tf, dn), tb = fminf(tb, up);
@@ -241,7 +192,7 @@ Stats shadow_walk(const Sim& S, V3 o, V3 d, double radius, Rule rule) {
   st.walks = 1;
   const RayF r = rayf(S, o, d);
   const float rad = (float)radius, D = sqrtf(r.dd);
-  const float mg = CULL_M * r.Sx * (1.0f + rad / D) + (S.q16 ? (2.0f + rad / D) * S.q_err : 0.0f);
+  const float mg = CULL_M * r.Sx * (1.0f + rad / D) + (S.q16 ? (2.0f + rad / D) * S.dev.q_err : 0.0f);
   float tb, tf, tm;
   nappe_bounds(S, r, rad, mg, tb, tf, tm);
   float tlo = 0.0f, thi = 1.0f + 1e-5f + r.mS / D, dil = r.mS;
@@ -256,10 +207,10 @@ Stats shadow_walk(const Sim& S, V3 o, V3 d, double radius, Rule rule) {
   // the band's own tolerance: 32 float32 ulps of the scene scale (the float32
   // geometry's error is below 10), + the 16-bit records' decoding error
   const float mgb = 32.0f * 5.96e-8f * r.Sx * (1.0f + rad / D);
-  const float mgq = mgb + (S.q16 ? (2.0f + rad / D) * S.q_err : 0.0f);
+  const float mgq = mgb + (S.q16 ? (2.0f + rad / D) * S.dev.q_err : 0.0f);
   std::vector<int> stk;
-  if (S.root == BVH_NONE) return st;
-  stk.push_back(S.root);
+  if (S.dev.bvh_root == BVH_NONE) return st;
+  stk.push_back(S.dev.bvh_root);
   while (!stk.empty()) {
     const int ref = stk.back();
     stk.pop_back();
@@ -323,9 +274,9 @@ int nearest(const Sim& S, V3 o, V3 d, double& best_t, bool& inside, Stats& st) {
     double t;
     if (plane_hit(S.obj[i], o, d, t) && t < best_t && vr(vsc(d, t)) < S.maxd) best_t = t, besti = (int)i, inside = false;
   }
-  if (S.root == BVH_NONE) return besti;
+  if (S.dev.bvh_root == BVH_NONE) return besti;
   const RayF r = rayf(S, o, d);
-  std::vector<int> stk{S.root};
+  std::vector<int> stk{S.dev.bvh_root};
   while (!stk.empty()) {
     const int ref = stk.back();
     stk.pop_back();
@@ -375,46 +326,30 @@ int main(int argc, char** argv) {
   rtxcli::load_world(argv[1], sc);
   const rtx_camera_desc cam = rtxcli::load_camera(argv[2]);
   Sim S;
-  S.obj = sc.objects;
-  S.lights = sc.lights;
-  S.maxd = sc.desc.max_distance;
-  S.build(true);
+  S.build(sc.desc, true);
   printf("scene: %zu spheres, %zu nodes, %zu slots, stack %d, q16 %d, q_err %.3g, sph_scale %.3g\n", S.sph64.size(),
-         S.bb->nodes.size(), S.bb->slot_obj.size(), S.bb->stack + 1, (int)S.q16, S.q_err, S.sph_scale);
-  // the light buffer and the raise buffer (RAISE_N cells per face side; default as rtx_scene_upload: 12 / 160)
+         S.bb->nodes.size(), S.bb->slot_obj.size(), S.bb->stack + 1, (int)S.q16, S.dev.q_err, S.dev.sph_scale);
+  // the light buffer and the raise buffer as rtx_scene_upload chooses them; COVER_N / RAISE_N (cells per face
+  // side) and PER_SPHERE (per-sphere raise lists) override its choice
   const int nl = (int)S.lights.size();
-  std::vector<double> lp, lr, lf;
-  for (const rtx_light_desc& L : S.lights) {
-    lp.insert(lp.end(), {L.position[0], L.position[1], L.position[2]});
-    lr.push_back(L.radius);
-    double fl = INFINITY;                          // the nearest object surface (rtx_capi.cpp raise_floor)
-    for (const rtx_object_desc& o : S.obj) {
-      if (o.type == RTX_SPHERE) {
-        const double w[3] = {o.center[0] - L.position[0], o.center[1] - L.position[1], o.center[2] - L.position[2]};
-        fl = std::min(fl, sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) - o.radius);
-      } else if (o.type == RTX_PLANE) {
-        const double fn = sqrt(o.front[0] * o.front[0] + o.front[1] * o.front[1] + o.front[2] * o.front[2]);
-        fl = std::min(fl, fabs((L.position[0] - o.point[0]) * o.front[0] + (L.position[1] - o.point[1]) * o.front[1] +
-                               (L.position[2] - o.point[2]) * o.front[2]) / fn);
-      } else {
-        fl = 0.0;
-      }
-    }
-    lf.push_back(std::max(0.0, 0.99 * fl));
+  pack_lights(&sc.desc, S);
+  S.lfloor = raise_floors(&sc.desc);
+  choose_light_buffer(S);
+  if (getenv("COVER_N"))
+    S.lb = build_light_buffer(*S.bb, S.dev.bvh_root, S.light_pos(), nl, atoi(getenv("COVER_N")), 1u << 30, S.lrad.data());
+  if (getenv("RAISE_N") || getenv("PER_SPHERE")) {
+    const int raise_n = getenv("RAISE_N") ? atoi(getenv("RAISE_N")) : (small_scene(S) ? 12 : RTX_RBUF_GLOBAL_N);
+    S.dev.rbuf_sphere = getenv("PER_SPHERE") != nullptr;
+    S.rb = build_raise_buffer(*S.bb, S.dev.bvh_root, S.light_pos(), S.lrad.data(), S.lfloor.data(), nl, raise_n,
+                              (size_t)1 << 30, S.dev.rbuf_sphere != 0);
+  } else {
+    choose_raise_buffer(S);
   }
-  const int cover_n = getenv("COVER_N") ? atoi(getenv("COVER_N")) : (S.sph64.size() <= 512 ? 24 : 160);
-  const int raise_n = getenv("RAISE_N") ? atoi(getenv("RAISE_N")) : (S.sph64.size() <= 512 ? 12 : 160);
-  LightBuffer lbc = build_light_buffer(*S.bb, S.root, reinterpret_cast<const double(*)[3]>(lp.data()), nl, cover_n,
-                                       1u << 30, lr.data());
-  std::vector<double> floors;
-  RaiseBuffer rbf = build_raise_buffer(*S.bb, S.root, reinterpret_cast<const double(*)[3]>(lp.data()), lr.data(),
-                                       lf.data(), nl, raise_n, (size_t)1 << 30, &floors, getenv("PER_SPHERE") != nullptr);
-  const std::vector<uint16_t> gates = raise_gates(rbf, nl);
-  const bool flags = true;
+  pack_gates(S);
+  const bool per_sphere = S.dev.rbuf_sphere != 0;
   printf("light buffer n %d: %d words per light; raise buffer n %d: %d words per light, floor %.4g (nearest surface "
          "%.4g), flags %d\n",
-         lbc.n, lbc.stride, rbf.n, rbf.stride, floors.empty() ? 0.0 : floors[0], lf.empty() ? 0.0 : lf[0] / 0.99,
-         (int)flags);
+         S.lb.n, S.lb.stride, S.rb.n, S.rb.stride, S.rb.n ? raise_floor(S.rb, 0) : 0.0, S.lfloor[0] / 0.99, 1);
   double rs_walks = 0, rs_cover = 0, rs_p = 0, rs_m = 0, rs_fb = 0, rs_union = 0, rs_band = 0, rs_scan = 0, rs_lookups = 0;
   std::vector<int> scan_hist, need_b2, need_b1, need_m;   // per shadow walk (raise-list entries read / needed)
   std::vector<std::vector<int32_t>> cover_seq;      // per shadow walk: the light buffer's cell
@@ -470,12 +405,11 @@ int main(int argc, char** argv) {
           const int li = (int)(&L - S.lights.data());
           const double dl[3] = {lt.x, lt.y, lt.z};
           rs_walks++;
-          if (lbc.n && rbf.n) {
-            const lbuf_host::Lists ls = lbuf_host::shadow_lists(lbc.words.data() + (size_t)lbc.stride * li, lbc.n,
-                                                                rbf.words.data() + (size_t)rbf.stride * li,
-                                                                gates.data() + (size_t)6 * rbf.n * rbf.n * li, rbf.n, dl,
-                                                          raise_floor2(rbf, li), raise_lf2(rbf, li),
-                                                          getenv("PER_SPHERE") != nullptr);
+          if (S.lb.n && S.rb.n) {
+            const LightDev& ld = S.HostScene::lights[li];   // (the gates and floats as the device reads them)
+            const lbuf_host::Lists ls = lbuf_host::shadow_lists(
+                S.lb.words.data() + (size_t)S.lb.stride * li, S.lb.n, S.rb.words.data() + (size_t)S.rb.stride * li,
+                S.gates.data() + (size_t)S.dev.rgate_stride * li + 8, S.rb.n, dl, ld.raise_f2, ld.raise_lf2, per_sphere);
             if (ls.fallback) {
               rs_fb++;
             } else {
@@ -485,7 +419,7 @@ int main(int argc, char** argv) {
               rs_scan += ls.scanned;
               std::vector<int32_t> un = ls.cover;
               for (const auto* v : {&ls.b2, &ls.b1, &ls.m}) un.insert(un.end(), v->begin(), v->end());
-              if (getenv("PER_SPHERE")) {
+              if (per_sphere) {
                 for (int32_t r : ls.cover) rs_band += ((~r) & 3) + 1;
                 rs_band += ls.b2.size() + ls.b1.size() + ls.m.size();
                 un = ls.cover;

@@ -92,7 +92,7 @@ void lane_start(const Sim& S, Lane& L, bool ext, V3 o, V3 d) {
   } else {
     L.thi = 1.0f + 1e-5f + L.r.mS / (float)D;
   }
-  L.ref = S.root;
+  L.ref = S.dev.bvh_root;
 }
 
 void lane_node(const Sim& S, Lane& L) {
@@ -244,7 +244,7 @@ uint32_t ray_key(const Sim& S, const WRay& r, bool oct_only, bool morton_only) {
   uint32_t m = 0;
   const double p[3] = {r.o.x, r.o.y, r.o.z};
   for (int a = 0; a < 3; a++) {
-    const double lo = S.root_c[a] - S.root_h[a], w = 2.0 * S.root_h[a];
+    const double lo = S.dev.root_c[a] - S.dev.root_h[a], w = 2.0 * S.dev.root_h[a];
     const double f = std::min(std::max((p[a] - lo) / w, 0.0), 0.999999);
     m |= spread10((uint32_t)(f * 1024)) << a;
   }
@@ -295,10 +295,7 @@ int main(int argc, char** argv) {
   rtxcli::load_world(argv[1], sc);
   const rtx_camera_desc cam = rtxcli::load_camera(argv[2]);
   Sim S;
-  S.obj = sc.objects;
-  S.lights = sc.lights;
-  S.maxd = sc.desc.max_distance;
-  S.build(true);
+  S.build(sc.desc, true);
   printf("scene: %zu spheres, %zu nodes, %zu leaf slots, stack %d, q16 %d, tree %s\n", S.sph64.size(),
          S.bb->nodes.size(), S.bb->slot_obj.size(), S.bb->stack + 1, (int)S.q16,
          getenv("WAVE_SIM_TREE") ? getenv("WAVE_SIM_TREE") : "library rule");
