@@ -81,6 +81,11 @@ module RTX
   extern 'int rtx_intersect(void*, int, void*, void*, void*)'
   extern 'int rtx_lit_area_device(void*, int, void*, void*, void*, void*, void*, void*)'
   extern 'int rtx_lit_area(void*, int, void*, void*, void*, void*, void*)'
+  # ---- batched Camera#lens_func / RayTracer#rt_map (scene and camera)
+  extern 'int rtx_lens_rays_device(void*, int, int, int, int, unsigned long long, int, void*, void*)'
+  extern 'int rtx_lens_rays(void*, int, int, int, int, unsigned long long, int, void*)'
+  extern 'int rtx_rt_map_device(void*, int, unsigned long long, void*, void*, void*, void*, void*, void*, void*, void*, void*)'
+  extern 'int rtx_rt_map(void*, int, unsigned long long, void*, void*, void*, void*, void*, void*, void*, void*)'
   extern 'int rtx_lpt_plan(void*, int, int, void*, int, void*)'
   extern 'int rtx_device_count()'
   extern 'int rtx_sync(void*, void*)'

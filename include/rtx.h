@@ -309,6 +309,65 @@ rtx_status rtx_lit_area_device(rtx_context* ctx, int32_t n, const double* d_targ
 rtx_status rtx_lit_area(rtx_context* ctx, int32_t n, const double* targets, const double* lights,
                         double* area, double* color, int32_t* status);
 
+/* Batched Camera#lens_func and RayTracer#rt_map: a ray tree
+ * node by node through public calls, lens_func -> rt_map* -> rt_reduce.  Both
+ * need an uploaded scene and a camera.  The *_device forms take device memory
+ * and are async on hip_stream; the host forms are synchronous and do not go
+ * through rtx_sync.  Neither records a raise in rtx_sync's state.
+ *
+ * Camera#lens_func(x, y, sample) (camera.rb:129-151) for pixels [x0,x1) x [y0,y1):
+ * rays: double[rows][cols][6] = Ray#front (not normalized), Ray#position, rows
+ * top-down as rtx_render.  The rays a render of the same seed traces for that
+ * sample (the render's own lens_target / lens_ray).  RTX_EINVAL as rtx_first_hit:
+ * an empty or out-of-frame rectangle, a sample outside [0, max(pre_sample_times,
+ * max_sample_times)), a NULL buffer, or no scene or camera uploaded. */
+rtx_status rtx_lens_rays_device(rtx_context* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                                uint64_t seed, int32_t sample, double* d_rays, void* hip_stream);
+rtx_status rtx_lens_rays(rtx_context* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                         uint64_t seed, int32_t sample, double* rays);
+
+/* RayTracer#rt_map (ray_tracer.rb:50-164), one call per item, n items.  The
+ * camera gives monte_carlo_diffusion_times = pt, as in rtx_trace.
+ * Inputs:
+ *   rays:  double[n][6] front, position, as rtx_trace; required.
+ *   att:   double[n][3] the item's attenuation; NULL = (1, 1, 1).
+ *   keys:  int32[n][4] = x, y, sample (the RNG key of the tree), remaining trace_depth; required.
+ *   paths: uint64[n] ray-path id; NULL = 1 (a root).
+ * Outputs, with CMAX = 2 + pt and LMAX = max(n_lights, 1):
+ *   info:        int32[n][6] = {status, kind, object, n_children, n_leaves, direction}; required.
+ *   children:    double[n][CMAX][9] = front, position, attenuation (item.att * att_x), in rt_map's
+ *                push order (reflection, refraction if any, path-tracing rays; :84-112,
+ *                world_object.rb:76-90), compacted.  Every child's depth is the item's - 1.
+ *   child_paths: uint64[n][CMAX] = path * (pt + 3) + slot; slot 1 reflection, 2 refraction,
+ *                3 + k path-tracing ray k: the slot identifies each compacted child.
+ *   leaves:      double[n][LMAX][3] = the colours rt_map appends (:60-75 the fired highlights,
+ *                :154-158 the local-lighting leaf), in order, times the item's attenuation.
+ *   children, child_paths and leaves may each be NULL.  Unused slots are zeros.
+ * kind: 0 dead (depth <= 0 || att.r < 0.0001, :52; nothing else is evaluated), 1 highlight
+ *   (n_leaves = fired lights, no children), 2 miss, 3 hit with at least one lit light (one leaf),
+ *   4 hit with none (pt path-tracing children, no leaf).  object and direction as rtx_intersect,
+ *   -1 unless kind is 3 or 4.
+ * rt_map returns children that die on their next pop (depth 0, a tiny attenuation); so does
+ * this call: the engines' early drops are not applied and every child is built in full.
+ * status (info[0]) is the rtx_status of the first raise of that rt_map call in the reference's
+ * order: high_lights (world.rb:83-98: per light the cos zero-vector check, then the lit_area
+ * acos of a fired light), intersect, intersect_parameters (n.normalize, reflection, refraction;
+ * world_object.rb:121-137), local_lights' acos (sphere.rb:45-46, under "exact_raises" as in a
+ * render), then path_tracing's vertical_vector or local_lighting's normalize and texture lookup.
+ * A raising item has kind -1, object and direction -1, counts 0, quiet NaN in all its child and
+ * leaf slots and 0 in its child paths; other items are unaffected.  rt_reduce's "color greater
+ * than 1" (:292-298) is not part of rt_map and is never reported.
+ * n == 0 is RTX_OK; RTX_EINVAL for n < 0, a missing required pointer, or no scene or camera.
+ * The device call returns RTX_OK whatever the statuses hold.  The host call fills the buffers,
+ * returns the status of the first raising item by index (RTX_OK if none) and names that index
+ * in rtx_last_error. */
+rtx_status rtx_rt_map_device(rtx_context* ctx, int32_t n, uint64_t seed, const double* d_rays, const double* d_att,
+                             const int32_t* d_keys, const uint64_t* d_paths, int32_t* d_info, double* d_children,
+                             uint64_t* d_child_paths, double* d_leaves, void* hip_stream);
+rtx_status rtx_rt_map(rtx_context* ctx, int32_t n, uint64_t seed, const double* rays, const double* att,
+                      const int32_t* keys, const uint64_t* paths, int32_t* info, double* children,
+                      uint64_t* child_paths, double* leaves);
+
 /* Longest-processing-time split of n_tiles tiles (costs[t]) over nranks:
  * tiles by decreasing cost (ties: lower index), each to the rank with the
  * least total so far (ties: fewer tiles, lower rank); every list ascending and

@@ -96,6 +96,11 @@ SIGNATURES = [
     ("rtx_intersect", _I, [_P, _I, _DP, C.POINTER(C.c_int32), _DP]),
     ("rtx_lit_area_device", _I, [_P, _I, _P, _P, _P, _P, _P, _P]),
     ("rtx_lit_area", _I, [_P, _I, _DP, _DP, _DP, _DP, C.POINTER(C.c_int32)]),
+    ("rtx_lens_rays_device", _I, [_P, _I, _I, _I, _I, _U64, _I, _P, _P]),
+    ("rtx_lens_rays", _I, [_P, _I, _I, _I, _I, _U64, _I, _DP]),
+    ("rtx_rt_map_device", _I, [_P, _I, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("rtx_rt_map", _I, [_P, _I, _U64, _DP, _DP, C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                        _DP, C.POINTER(C.c_uint64), _DP]),
     ("rtx_lpt_plan", _I, [C.POINTER(C.c_int64), _I, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32)]),
     ("rtx_device_count", _I, []),
     ("rtx_sync", _I, [_P, _P]),

@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librtx.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("rtx_kernels.hip", "rtx_levels.hip", "rtx_aov.hip", "rtx_query.hip", "rtx_capi.cpp")]
+SOURCES = [os.path.join(CSRC, f) for f in ("rtx_kernels.hip", "rtx_levels.hip", "rtx_aov.hip", "rtx_query.hip", "rtx_rtmap.hip",
+                                                "rtx_capi.cpp")]
 HEADERS = [os.path.join(CSRC, f) for f in ("rtx_scene.h", "rtx_vec3.h", "rtx_launch.h", "rtx_sched.h", "rtx_device.h", "rtx_bvh_build.h",
                                              "rtx_scene_build.h")] + [
     os.path.join(ROOT, "include", "rtx.h")]

@@ -103,6 +103,18 @@ class RayTracer:
         rays = np.array([ray.front.to_a() + ray.position.to_a()], np.float64)
         return Vec3(*self._r.path_trace(rays)[0])
 
+    def rt_map(self, rays, att=None, keys=None, paths=None):
+        """RayTracer#rt_map (ray_tracer.rb:50-164), one call per item: rays [n, 6] =
+        (front, position), att [n, 3] or None (ones), keys [n, 4] = (x, y, sample,
+        remaining trace_depth), paths [n] or None (roots).  A dict of arrays
+        (Renderer.rt_map): "status", "kind", "object", "n_children", "n_leaves",
+        "direction" [n]; "children" [n, CMAX, 9] = (front, position, attenuation),
+        each one level deeper; "child_paths" [n, CMAX]; "leaves" [n, LMAX, 3].
+        RtxError for the first item whose rt_map raises."""
+        if keys is None:
+            raise ValueError("rt_map needs keys: (x, y, sample, remaining trace_depth) per ray")
+        return self._r.rt_map(rays, keys, att=att, paths=paths, seed=self.seed)
+
     def trace_many(self, fronts, positions, keys):
         """Batched trace_sync: fronts/positions [n, 3], keys [n, 3] = (x, y, sample)."""
         rays = np.concatenate([np.asarray(fronts, np.float64), np.asarray(positions, np.float64)], axis=1)
@@ -141,6 +153,11 @@ class Camera:
         {"object", "direction", "data": int32 [H, W]; "depth": [H, W];
         "position", "normal", "albedo": [H, W, 3]} (Renderer.first_hit)."""
         return self._r.first_hit(x0, y0, x1, y1, seed=self.seed, sample=sample)
+
+    def lens_rays(self, sample=0, x0=0, y0=0, x1=None, y1=None):
+        """lens_func(x, y, sample) (camera.rb:129-151) for every pixel of the region:
+        [H, W, 6] = (front, position), the rays render_at traces for that sample."""
+        return self._r.lens_rays(x0, y0, x1, y1, seed=self.seed, sample=sample)
 
     # -- camera.rb:101-110 + save_image (:36-39)
     def render_sync(self, file_path=None, png_gem_blend=True):

@@ -1439,6 +1439,137 @@ rtx_status rtx_lit_area(rtx_context* c, int32_t n, const double* targets, const 
   return RTX_OK;
 }
 
+// Batched Camera#lens_func and RayTracer#rt_map (rtx_rtmap.hip).  Scene and
+// camera; like the World queries they record nothing in the device's raise
+// record and take no work counter or ray stack, so prep() is not theirs.
+static rtx_status prep_rt_map(rtx_context* c, KParams& p, uint64_t seed) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  memset(&p, 0, sizeof p);
+  p.scene = c->scene;
+  p.cam = c->d_cam;
+  p.seed = seed;
+  p.exact_raises = (int32_t)c->opt_exact_raises;
+  return RTX_OK;
+}
+
+// The argument checks of rtx_first_hit, shared by the device and the host form of rtx_lens_rays.
+static rtx_status lens_rays_args(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t sample,
+                                 const double* rays) {
+  if (!c) return RTX_EINVAL;
+  if (!rays) return fail(c, RTX_EINVAL, "null ray buffer");
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  if (x0 < 0 || y0 < 0 || x1 > c->cam.width || y1 > c->cam.height || x0 >= x1 || y0 >= y1)
+    return fail(c, RTX_EINVAL, "region [%d,%d)x[%d,%d) empty or outside the %dx%d image", x0, x1, y0, y1,
+                c->cam.width, c->cam.height);
+  const int ms = std::max(c->cam.pre, c->cam.max_samples);
+  if (sample < 0 || sample >= ms) return fail(c, RTX_EINVAL, "sample %d outside [0, %d)", sample, ms);
+  return RTX_OK;
+}
+
+rtx_status rtx_lens_rays_device(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint64_t seed,
+                                int32_t sample, double* d_rays, void* stream) {
+  rtx_status s = lens_rays_args(c, x0, y0, x1, y1, sample, d_rays);
+  if (s) return s;
+  KParams p;
+  if ((s = prep_rt_map(c, p, seed))) return s;
+  p.x0 = x0;
+  p.nx = x1 - x0;
+  p.y0 = y0;
+  p.nrows = y1 - y0;
+  HIPCHK(c, launch_lens_rays(p, sample, d_rays, (hipStream_t)stream));
+  return RTX_OK;
+}
+
+rtx_status rtx_lens_rays(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint64_t seed,
+                         int32_t sample, double* rays) {
+  rtx_status s = lens_rays_args(c, x0, y0, x1, y1, sample, rays);
+  if (s) return s;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)(x1 - x0) * (size_t)(y1 - y0) * 6 * sizeof(double);
+  if ((s = ensure_scratch(c, bytes))) return s;
+  if ((s = rtx_lens_rays_device(c, x0, y0, x1, y1, seed, sample, c->d_scratch, nullptr))) return s;
+  // (a stream-ordered blocking copy, as rtx_first_hit: no rtx_sync)
+  HIPCHK(c, hipMemcpy(rays, c->d_scratch, bytes, hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+
+// The argument checks the device and the host form of rtx_rt_map share.  *go: there is work.
+static rtx_status rt_map_args(rtx_context* c, int32_t n, const double* rays, const int32_t* keys, const int32_t* info,
+                              bool* go) {
+  *go = false;
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative item count");
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  if (n == 0) return RTX_OK;
+  if (!rays) return fail(c, RTX_EINVAL, "null rays");
+  if (!keys) return fail(c, RTX_EINVAL, "null keys");
+  if (!info) return fail(c, RTX_EINVAL, "null info buffer");
+  *go = true;
+  return RTX_OK;
+}
+
+rtx_status rtx_rt_map_device(rtx_context* c, int32_t n, uint64_t seed, const double* d_rays, const double* d_att,
+                             const int32_t* d_keys, const uint64_t* d_paths, int32_t* d_info, double* d_children,
+                             uint64_t* d_child_paths, double* d_leaves, void* stream) {
+  bool go;
+  rtx_status s = rt_map_args(c, n, d_rays, d_keys, d_info, &go);
+  if (s || !go) return s;
+  KParams p;
+  if ((s = prep_rt_map(c, p, seed))) return s;
+  p.nrays = n;
+  HIPCHK(c, launch_rt_map(p, sph_mode(c), d_rays, d_att, d_keys, d_paths, d_info, d_children, d_child_paths, d_leaves,
+                          (hipStream_t)stream));
+  return RTX_OK;
+}
+
+rtx_status rtx_rt_map(rtx_context* c, int32_t n, uint64_t seed, const double* rays, const double* att,
+                      const int32_t* keys, const uint64_t* paths, int32_t* info, double* children,
+                      uint64_t* child_paths, double* leaves) {
+  bool go;
+  rtx_status s = rt_map_args(c, n, rays, keys, info, &go);
+  if (s || !go) return s;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n, cmax = 2 + (size_t)c->cam.pt, lmax = (size_t)std::max(1, c->scene.n_light);
+  // (the 8-byte values first, then the int32 ones: every buffer 8-byte aligned)
+  const size_t rb = N * 6 * sizeof(double), ab = att ? N * 3 * sizeof(double) : 0, pb = paths ? N * sizeof(uint64_t) : 0;
+  const size_t cb = children ? N * cmax * 9 * sizeof(double) : 0, qb = child_paths ? N * cmax * sizeof(uint64_t) : 0;
+  const size_t lb = leaves ? N * lmax * 3 * sizeof(double) : 0;
+  const size_t kb = N * 4 * sizeof(int32_t), ib = N * 6 * sizeof(int32_t);
+  if ((s = ensure_scratch(c, rb + ab + pb + cb + qb + lb + kb + ib))) return s;
+  char* at = reinterpret_cast<char*>(c->d_scratch);
+  auto take = [&](size_t bytes) {
+    char* q = bytes ? at : nullptr;
+    at += bytes;
+    return q;
+  };
+  double* d_rays = reinterpret_cast<double*>(take(rb));
+  double* d_att = reinterpret_cast<double*>(take(ab));
+  uint64_t* d_paths = reinterpret_cast<uint64_t*>(take(pb));
+  double* d_children = reinterpret_cast<double*>(take(cb));
+  uint64_t* d_child_paths = reinterpret_cast<uint64_t*>(take(qb));
+  double* d_leaves = reinterpret_cast<double*>(take(lb));
+  int32_t* d_keys = reinterpret_cast<int32_t*>(take(kb));
+  int32_t* d_info = reinterpret_cast<int32_t*>(take(ib));
+  HIPCHK(c, hipMemcpy(d_rays, rays, rb, hipMemcpyHostToDevice));
+  if (att) HIPCHK(c, hipMemcpy(d_att, att, ab, hipMemcpyHostToDevice));
+  if (paths) HIPCHK(c, hipMemcpy(d_paths, paths, pb, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(d_keys, keys, kb, hipMemcpyHostToDevice));
+  if ((s = rtx_rt_map_device(c, n, seed, d_rays, d_att, d_keys, d_paths, d_info, d_children, d_child_paths, d_leaves,
+                             nullptr)))
+    return s;
+  // (stream-ordered blocking copies, as rtx_first_hit: no rtx_sync)
+  HIPCHK(c, hipMemcpy(info, d_info, ib, hipMemcpyDeviceToHost));
+  if (children) HIPCHK(c, hipMemcpy(children, d_children, cb, hipMemcpyDeviceToHost));
+  if (child_paths) HIPCHK(c, hipMemcpy(child_paths, d_child_paths, qb, hipMemcpyDeviceToHost));
+  if (leaves) HIPCHK(c, hipMemcpy(leaves, d_leaves, lb, hipMemcpyDeviceToHost));
+  for (int32_t i = 0; i < n; i++)
+    if (info[6 * (size_t)i])
+      return fail(c, (rtx_status)info[6 * (size_t)i], "%s at item %d",
+                  rtx_status_string((rtx_status)info[6 * (size_t)i]), i);
+  return RTX_OK;
+}
+
 rtx_status rtx_lpt_plan(const int64_t* costs, int32_t n_tiles, int32_t nranks, int32_t* plan, int32_t cap,
                         int32_t* per_rank) {
   if (n_tiles < 0 || nranks < 1 || (n_tiles > 0 && !costs) || !per_rank) return RTX_EINVAL;

@@ -237,5 +237,14 @@ hipError_t launch_intersect(KParams p, int mode, int32_t* d_ids, double* d_geom,
 // of the target's first raise; nothing goes to p.err).
 hipError_t launch_lit_area(KParams p, int mode, const double* d_targets, const double* d_lights, double* d_area,
                            double* d_color, int32_t* d_status, hipStream_t s);
+// Batched Camera#lens_func and RayTracer#rt_map (rtx_rtmap.hip).
+// The rays of camera sample `sample` for the region of `p`: d_rays double[nrows][nx][6].
+hipError_t launch_lens_rays(const KParams& p, int32_t sample, double* d_rays, hipStream_t s);
+// One rt_map call per item over p.nrays items (p.cam: monte_carlo_diffusion_times; p.seed): d_rays [n][6],
+// d_att [n][3] or null, d_keys int32[n][4], d_paths [n] or null -> d_info int32[n][6], and, each or null,
+// d_children [n][2 + pt][9], d_child_paths [n][2 + pt], d_leaves [n][max(n_light, 1)][3].  Nothing goes to p.err.
+hipError_t launch_rt_map(KParams p, int mode, const double* d_rays, const double* d_att, const int32_t* d_keys,
+                         const uint64_t* d_paths, int32_t* d_info, double* d_children, uint64_t* d_child_paths,
+                         double* d_leaves, hipStream_t s);
 
 }  // namespace rtx

@@ -157,6 +157,58 @@ class Renderer:
             self._check(st)
         return area, color, status
 
+    def lens_rays(self, x0=0, y0=0, x1=None, y1=None, seed=1, sample=0):
+        """Camera#lens_func(x, y, sample) for the region (rtx_lens_rays): float64
+        [H, W, 6] = (front, position), row = y, top first: the rays a render of the
+        same seed traces for that sample."""
+        x1 = self.width if x1 is None else x1
+        y1 = self.height if y1 is None else y1
+        rays = np.empty((max(y1 - y0, 0), max(x1 - x0, 0), 6), np.float64)
+        self._check(self.lib.rtx_lens_rays(self.h, x0, y0, x1, y1, seed, sample, _dp(rays)))
+        return rays
+
+    def rt_map(self, rays, keys, att=None, paths=None, seed=1, check=True, children=True, child_paths=True,
+               leaves=True):
+        """RayTracer#rt_map, one call per item (rtx_rt_map).  rays [n, 6] = (front,
+        position); keys int32 [n, 4] = (x, y, sample, remaining trace_depth); att
+        [n, 3] or None (ones); paths uint64 [n] or None (roots).  A dict of arrays:
+        ``status``, ``kind`` (0 dead, 1 highlight, 2 miss, 3 lit hit, 4 unlit hit,
+        -1 a raise), ``object``, ``n_children``, ``n_leaves``, ``direction`` int32
+        [n]; ``children`` [n, CMAX, 9] = (front, position, attenuation),
+        ``child_paths`` uint64 [n, CMAX], ``leaves`` [n, LMAX, 3], with CMAX = 2 +
+        monte_carlo_diffusion_times and LMAX = max(lights, 1); an output switched
+        off by its flag is None.  check=True raises RtxError for the first raising
+        item; check=False returns the statuses."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = len(rays)
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 4)
+        if len(keys) != n:
+            raise ValueError("one key per ray")
+        u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+        if att is not None:
+            att = np.ascontiguousarray(att, np.float64).reshape(-1, 3)
+            if len(att) != n:
+                raise ValueError("one attenuation per ray")
+        if paths is not None:
+            paths = np.ascontiguousarray(paths, np.uint64).reshape(-1)
+            if len(paths) != n:
+                raise ValueError("one path per ray")
+        cmax = 2 + self.camera.monte_carlo_diffusion_times
+        lmax = max(self._scene.desc.n_lights, 1)
+        info = np.zeros((n, 6), np.int32)
+        ch = np.empty((n, cmax, 9), np.float64) if children else None
+        cp = np.empty((n, cmax), np.uint64) if child_paths else None
+        lf = np.empty((n, lmax, 3), np.float64) if leaves else None
+        st = self.lib.rtx_rt_map(self.h, n, seed, _dp(rays), _dp(att) if att is not None else None,
+                                 keys.ctypes.data_as(i32p), paths.ctypes.data_as(u64p) if paths is not None else None,
+                                 info.ctypes.data_as(i32p), _dp(ch) if children else None,
+                                 cp.ctypes.data_as(u64p) if child_paths else None, _dp(lf) if leaves else None)
+        if st and (check or not info[:, 0].any()):   # (a status without a raising item: an argument or HIP error)
+            self._check(st)
+        out = split_rt_map(info)
+        out.update(children=ch, child_paths=cp, leaves=lf)
+        return out
+
     def count_work(self, seed=1):
         cnt = (C.c_uint64 * RTX_NCOUNT)()
         self._check(self.lib.rtx_count_work(self.h, seed, cnt))
@@ -191,6 +243,25 @@ class Renderer:
         self._check(self.lib.rtx_lit_area_device(self.h, n, C.c_void_p(d_targets or 0), C.c_void_p(d_lights or 0),
                                                  C.c_void_p(d_area or 0), C.c_void_p(d_color or 0),
                                                  C.c_void_p(d_status or 0), C.c_void_p(stream or 0)))
+
+    def lens_rays_device(self, d_rays, seed=1, sample=0, x0=0, y0=0, x1=None, y1=None, stream=None):
+        """rtx_lens_rays_device: d_rays float64 [rows, cols, 6] (device pointer)."""
+        x1 = self.width if x1 is None else x1
+        y1 = self.height if y1 is None else y1
+        self._check(self.lib.rtx_lens_rays_device(self.h, x0, y0, x1, y1, seed, sample, C.c_void_p(d_rays or 0),
+                                                  C.c_void_p(stream or 0)))
+
+    def rt_map_device(self, n, d_rays, d_att, d_keys, d_paths, d_info, d_children=None, d_child_paths=None,
+                      d_leaves=None, seed=1, stream=None):
+        """rtx_rt_map_device: d_rays float64 [n, 6], d_att None or float64 [n, 3], d_keys
+        int32 [n, 4], d_paths None or uint64 [n], d_info int32 [n, 6], and, each or None,
+        d_children float64 [n, CMAX, 9], d_child_paths uint64 [n, CMAX], d_leaves float64
+        [n, LMAX, 3] (device pointers).  Raises go to d_info only."""
+        self._check(self.lib.rtx_rt_map_device(self.h, n, seed, C.c_void_p(d_rays or 0), C.c_void_p(d_att or 0),
+                                               C.c_void_p(d_keys or 0), C.c_void_p(d_paths or 0),
+                                               C.c_void_p(d_info or 0), C.c_void_p(d_children or 0),
+                                               C.c_void_p(d_child_paths or 0), C.c_void_p(d_leaves or 0),
+                                               C.c_void_p(stream or 0)))
 
     def rows_per_rank(self, tile_rows, nranks):
         return self.lib.rtx_tiles_rows_per_rank(self.height, tile_rows, nranks)
@@ -275,6 +346,12 @@ def split_intersect(ids, geom):
     out = split_first_hit(ids, geom)
     out["delta"] = geom[..., 10:13]
     return out
+
+
+def split_rt_map(info):
+    """The named views of rtx_rt_map's info buffer [n, 6]."""
+    return {"status": info[..., 0], "kind": info[..., 1], "object": info[..., 2], "n_children": info[..., 3],
+            "n_leaves": info[..., 4], "direction": info[..., 5]}
 
 
 def render_multi(renderers, tile_rows=8, seed=1):
