@@ -322,6 +322,21 @@ __device__ __forceinline__ bool xr_band(const XrRay& x, float dd, float l, float
   return x.all || (l >= lo * lo * dd - e && l <= hi * hi * dd + e);
 }
 
+// xr_band for the two spheres of one packed pre-test step: bit 0 for the .x
+// halves, bit 1 for the .y halves; W their squared radii.  The same float32
+// operations on the same values, two per packed instruction where one exists.
+__device__ __forceinline__ uint32_t xr_band2(const XrRay& x, float dd, F2 l, F2 q, F2 sq, F2 W) {
+  const F2 R = {__builtin_amdgcn_sqrtf(W.x), __builtin_amdgcn_sqrtf(W.y)};
+  const F2 pk = {x.k, x.k}, pmb = {x.mb, x.mb}, pdd = {dd, dd}, p4 = {4e-6f, 4e-6f};
+  const F2 d = R - pk * F2{fabsf(q.x), fabsf(q.y)};
+  const F2 t = {fabsf(d.x), fabsf(d.y)};
+  const F2 tm = t - pmb, hi = t + pmb;
+  const F2 lo = {fmaxf(tm.x, 0.0f), fmaxf(tm.y, 0.0f)};
+  const F2 e = p4 * (sq + hi * hi) * pdd;
+  const F2 a = lo * lo * pdd - e, b = hi * hi * pdd + e;
+  return ((x.all || (l.x >= a.x && l.x <= b.x)) ? 1u : 0u) | ((x.all || (l.y >= a.y && l.y <= b.y)) ? 2u : 0u);
+}
+
 // ----------------------------------------------------------------- the query
 // One ordered walk over every object with ray (o, d), for every active lane.
 //   EXTEND: World#intersect — nearest hit (strict <, YAML order) -> best/besti.
@@ -538,14 +553,18 @@ __device__ __forceinline__ void push_cover(int* ci, double* cv, int& n, bool& ov
 
 // The float32 set-up of a walk's culls (§2.1 pre-test, §2.2 slab test), shared
 // by the hierarchy walk and the flat leaf scan.
-struct SlabRay {
+// WalkRay: what every walk's leaf test needs (the §2.1 pre-test's constants);
+// SlabRay adds the node part, the operands of the §2.2 slab test.
+struct WalkRay {
   float ox, oy, oz, dx, dy, dz, dd, Sx, ms2, mS, kline, qneg;
-  F2 pix, piy, piz, pax, pay, paz;   // packed operands of the slab test: {lo, hi} * {i, i} + {-a, -b} per axis
   bool fin;                          // false: a non-finite or zero ray, no float32 cull is valid
 };
+struct SlabRay : WalkRay {
+  F2 pix, piy, piz, pax, pay, paz;   // packed operands of the slab test: {lo, hi} * {i, i} + {-a, -b} per axis
+};
 
-__device__ __forceinline__ SlabRay slab_setup(const SceneDev& S, V3 o, V3 d) {
-  SlabRay s;
+// Returns |d|_1 (float32).
+__device__ __forceinline__ float walk_setup(const SceneDev& S, V3 o, V3 d, WalkRay& s) {
   s.ox = (float)o.x, s.oy = (float)o.y, s.oz = (float)o.z;
   s.dx = (float)d.x, s.dy = (float)d.y, s.dz = (float)d.z;
   s.dd = __builtin_fmaf(s.dx, s.dx, __builtin_fmaf(s.dy, s.dy, s.dz * s.dz));
@@ -554,8 +573,26 @@ __device__ __forceinline__ SlabRay slab_setup(const SceneDev& S, V3 o, V3 d) {
   s.mS = CULL_M * s.Sx;
   s.kline = s.dd * s.ms2;
   s.qneg = -CULL_M * s.Sx * sqrtf(s.dd);
+  return fabsf(s.dx) + fabsf(s.dy) + fabsf(s.dz);
+}
+
+// The set-up of a walk that slab-tests no node (the light buffer's, §3.18).  Its
+// finiteness test needs no reciprocal: with |d|_1 >= 2e-17 every component the
+// slab set-up would divide by is at least 1e-20 |d|_1 >= 2e-37 in magnitude (and
+// finite, as |d|^2 is), so its reciprocals are finite: fin here implies
+// slab_setup's fin.  The few rays more that it turns away (|d|_1 < 2e-17) take the
+// caller's fallback, the hierarchy walk, which gives the same bits.
+__device__ __forceinline__ WalkRay leaf_setup(const SceneDev& S, V3 o, V3 d) {
+  WalkRay s;
+  const float l1 = walk_setup(S, o, d, s);
+  s.fin = __builtin_isfinite(s.dd) && __builtin_isfinite(s.Sx) && l1 >= 2e-17f;
+  return s;
+}
+
+__device__ __forceinline__ SlabRay slab_setup(const SceneDev& S, V3 o, V3 d) {
+  SlabRay s;
   // slab set-up: reciprocal direction and the dilated origin terms
-  const float l1 = fabsf(s.dx) + fabsf(s.dy) + fabsf(s.dz);
+  const float l1 = walk_setup(S, o, d, s);
   const float tiny = 1e-20f * l1;
   const float ex = fabsf(s.dx) < tiny ? copysignf(tiny, s.dx) : s.dx;
   const float ey = fabsf(s.dy) < tiny ? copysignf(tiny, s.dy) : s.dy;
@@ -703,7 +740,7 @@ __device__ __forceinline__ void leaf_records(const QLeaf& l, int v, float4& cx, 
 // One leaf (reference lf < 0): the §2.1 pre-test of its spheres, the exact
 // test for those not ruled out, then the nearest-hit update or the cover list.
 template <int BS, typename LP, typename XP, typename OP>
-__device__ __forceinline__ void walk_leaf(int lf, LP leaf4, XP x64, OP xobj, const SlabRay& s, bool ext, V3 o, V3 d,
+__device__ __forceinline__ void walk_leaf(int lf, LP leaf4, XP x64, OP xobj, const WalkRay& s, bool ext, V3 o, V3 d,
                                           V3 dn, double r, double r2, V3 L, double radius, double& best, int& besti,
                                           V3& bhit, bool& bin, float& thi, uint32_t& err, int* ci, double* cv,
                                           int& ncov, bool& ovf, bool xr, float qerr, int after = -1) {
@@ -732,9 +769,7 @@ __device__ __forceinline__ void walk_leaf(int lf, LP leaf4, XP x64, OP xobj, con
     const bool m0 = l.x > rr.x || (q.x < s.qneg && sq.x > wm.x);   // misses the line, or wholly behind
     const bool m1 = l.y > rr.y || (q.y < s.qneg && sq.y > wm.y);
     keep |= (m0 ? 0u : 1u << (2 * h)) | (m1 ? 0u : 2u << (2 * h));
-    if (xr)                                         // exact_raises: rho within mg of |R - r1|
-      xkeep |= (xr_band(xrr, s.dd, l.x, q.x, sq.x, __builtin_amdgcn_sqrtf(Wr.x)) ? 1u << (2 * h) : 0u) |
-               (xr_band(xrr, s.dd, l.y, q.y, sq.y, __builtin_amdgcn_sqrtf(Wr.y)) ? 2u << (2 * h) : 0u);
+    if (xr) xkeep |= xr_band2(xrr, s.dd, l, q, sq, Wr) << (2 * h);   // exact_raises: rho within mg of |R - r1|
   }
   keep &= (1u << cnt) - 1u;
   xkeep &= (1u << cnt) - 1u;
@@ -811,7 +846,7 @@ __device__ __forceinline__ int lbuf_cell(float vx, float vy, float vz, int n, in
 // (xr_band) of every sphere of one leaf, whatever its factor, and the binary64
 // test (penumbra_raises) of those it keeps.
 template <typename LP, typename XP>
-__device__ __forceinline__ void leaf_raises(int lf, LP leaf4, XP x64, const SlabRay& s, const XrRay& xrr, V3 o, V3 d,
+__device__ __forceinline__ void leaf_raises(int lf, LP leaf4, XP x64, const WalkRay& s, const XrRay& xrr, V3 o, V3 d,
                                             double radius, uint32_t& err) {
   const int v = ~lf;
   const int slot0 = (v >> 2) * BVH_LEAF;
@@ -829,8 +864,7 @@ __device__ __forceinline__ void leaf_raises(int lf, LP leaf4, XP x64, const Slab
     const F2 sq = __builtin_elementwise_fma(ocx, ocx, __builtin_elementwise_fma(ocy, ocy, ocz * ocz));
     const F2 q = __builtin_elementwise_fma(ocx, pdx, __builtin_elementwise_fma(ocy, pdy, ocz * pdz));
     const F2 l = __builtin_elementwise_fma(sq, pdd, -(q * q));
-    xkeep |= (xr_band(xrr, s.dd, l.x, q.x, sq.x, __builtin_amdgcn_sqrtf(Wr.x)) ? 1u << (2 * h) : 0u) |
-             (xr_band(xrr, s.dd, l.y, q.y, sq.y, __builtin_amdgcn_sqrtf(Wr.y)) ? 2u << (2 * h) : 0u);
+    xkeep |= xr_band2(xrr, s.dd, l, q, sq, Wr) << (2 * h);
   }
   xkeep &= (1u << cnt) - 1u;
   while (xkeep && !(err & 0xffu)) {
@@ -862,7 +896,7 @@ __device__ __forceinline__ void sphere_record(const QLeaf& l, int slot, float& c
 // exact_raises for one sphere of the raise buffer's per-sphere lists (slot):
 // the band test and, when it keeps the sphere, the binary64 test.
 template <typename LP, typename XP>
-__device__ __forceinline__ void sphere_raises(int slot, LP leaf4, XP x64, const SlabRay& s, const XrRay& xrr, V3 o,
+__device__ __forceinline__ void sphere_raises(int slot, LP leaf4, XP x64, const WalkRay& s, const XrRay& xrr, V3 o,
                                               V3 d, double radius, uint32_t& err) {
   float cx, cy, cz, w;
   sphere_record(leaf4, slot, cx, cy, cz, w);
@@ -887,12 +921,12 @@ __device__ __forceinline__ void sphere_raises(int slot, LP leaf4, XP x64, const 
 // floor^2 as float bits, 4 of padding, a gate per raise-buffer cell), in LDS
 // or global memory.
 constexpr float QA_SLACK = 0.7f;             // 8 x 0.0861 + the int-to-float rounding of the bits
-__device__ __forceinline__ bool raise_qa(float f2, float lf2, const SlabRay& s, float& qa) {
+__device__ __forceinline__ bool raise_qa(float f2, float lf2, const WalkRay& s, float& qa) {
   qa = 8.0f * (__builtin_fmaf((float)__float_as_int(s.dd), 1.0f / 8388608.0f, -127.0f) - lf2);
   // l >= floor (1 + 1e-4): |d|^2 >= floor^2 (1 + 2.1e-4), floor^2 rounded up
   return s.dd >= f2 * (1.0f + 2.1e-4f) && qa + QA_SLACK <= 254.0f;
 }
-__device__ __forceinline__ float raise_rq(float lf2, const SlabRay& s) { return 8.0f * (__log2f(s.dd) - lf2); }
+__device__ __forceinline__ float raise_rq(float lf2, const WalkRay& s) { return 8.0f * (__log2f(s.dd) - lf2); }
 
 // The raise buffer's lists (rtx_bvh_build.h build_raise_buffer): B2 and B1 at
 // the parent (raise-buffer) cell of the light buffer's cell (face, i, j) of
@@ -904,7 +938,7 @@ __device__ __forceinline__ float raise_rq(float lf2, const SlabRay& s) { return 
 // light buffer's own cell, walked with walk_leaf's band test, holds regime A.)
 template <typename LP, typename XP>
 __device__ __forceinline__ void raise_lists(const SceneDev& S, int light, const uint16_t* gates, LP leaf4, XP x64,
-                                            const SlabRay& s, const XrRay& xrr, V3 o, V3 d, double radius, int face,
+                                            const WalkRay& s, const XrRay& xrr, V3 o, V3 d, double radius, int face,
                                             int i, int j, float qa, float lf2, uint32_t& err) {
   const int nu = S.lbuf_n, nc = S.rbuf_n, cells = 6 * nc * nc;
   // parent cells: i / m as (int)((i + 0.5) / m) in float32 (no integer division: i, m < 2^12, so
@@ -1006,7 +1040,7 @@ __device__ __forceinline__ bool query_lbuf(const SceneDev& S, const uint16_t* lb
                                            double* cv, V3 o, V3 d, V3 L, double radius, double& best, int& besti,
                                            V3& bhit, bool& bin, double& total, uint32_t& err, bool xr = false,
                                            int light = 0, const uint16_t* gates = nullptr) {
-  const SlabRay s = slab_setup(S, o, d);
+  const WalkRay s = leaf_setup(S, o, d);        // (no node is slab-tested here)
   if (!s.fin) return false;
   // the cube-map cell of v = o - L = -d
   const int n = S.lbuf_n;
@@ -1083,7 +1117,7 @@ __device__ __forceinline__ bool query_lbuf(const SceneDev& S, const uint16_t* lb
 __device__ __forceinline__ int lit_area_raises_lbuf(const SceneDev& S, int light, V3 T, V3 L, double radius) {
   if (!(radius > 0.0) || S.n_sphere == 0) return 0;   // as lit_area_raises
   const V3 d = vsub(L, T);
-  const SlabRay s = slab_setup(S, T, d);
+  const WalkRay s = leaf_setup(S, T, d);
   if (!s.fin) return -1;
   int face, i, j;
   const int n = S.lbuf_n;
@@ -1382,15 +1416,22 @@ __device__ __forceinline__ Ray reflection(const Ray& ray, V3 nn, double c, V3 hi
 }
 
 // WorldObject#get_refraction_by_ray_and_n (world_object.rb:127-137).
-__device__ __forceinline__ bool refraction(const Ray& ray, V3 nn, double c, V3 hit, V3 refl, double rate,
-                                           Ray& out, uint32_t& err) {
+// refract_sin: sin_r = sin_i / rate; refraction_sin: the ray from a sin_r the caller has already.
+__device__ __forceinline__ double refract_sin(double c, double rate) {
   const double sin_i = sqrt(1.0 - c * c);        // 1 - cos**2
-  const double sin_r = sin_i / rate;
+  return sin_i / rate;
+}
+__device__ __forceinline__ bool refraction_sin(const Ray& ray, V3 nn, double sin_r, V3 hit, V3 refl, Ray& out,
+                                               uint32_t& err) {
   if (sin_r >= 1) return false;                  // total internal reflection
   const double r = rx_asin(sin_r);
   out.d = vadd(vsc(nn, -rx_cos(r)), vsc(vnorm(vadd(refl, ray.d), err), sin_r));
   out.o = vsub(hit, vsc(nn, EPS));
   return true;
+}
+__device__ __forceinline__ bool refraction(const Ray& ray, V3 nn, double c, V3 hit, V3 refl, double rate,
+                                           Ray& out, uint32_t& err) {
+  return refraction_sin(ray, nn, refract_sin(c, rate), hit, refl, out, err);
 }
 
 __device__ __forceinline__ V3 texcolor(const SceneDev& S, int tex, double hs, double vs, double uo,
@@ -1550,13 +1591,30 @@ __device__ __forceinline__ void emit(Stack& st, Item& pend, bool& has, uint32_t&
 // a lit light counts in nl and adds its colour, scaled by the clamped cosine, to lc.  The sums go in and out by
 // value: as reference parameters they cost k_render spilled registers.
 struct LightSum { V3 lc; int nl; };
+// x / n for a wave-uniform count n (the scene's lights, monte_carlo_diffusion_times): IEEE x / 1.0 is x for
+// every x, so n == 1 skips the division, on a scalar branch.
+__device__ __forceinline__ double div_count(double x, int n) {
+  if (n != 1) x = x / (double)n;
+  return x;
+}
+__device__ __forceinline__ V3 vdiv_count(V3 a, int n) {
+  if (n != 1) a = vdiv(a, (double)n);
+  return a;
+}
+// A light's share pw / lights of local_lighting's colour (world_object.rb:60).
+__device__ __forceinline__ double light_share(const SceneDev& S, double pw) { return div_count(pw, S.n_light); }
+// vdiv(a, k) for a per-lane count 1 <= k <= the scene's lights (lit lights, fired lights): one light, k = 1.
+__device__ __forceinline__ V3 vdiv_lights(const SceneDev& S, V3 a, int k) {
+  if (S.n_light == 1) return a;
+  return vdiv(a, (double)k);
+}
 __device__ __forceinline__ LightSum light_term(const SceneDev& S, const LightDev& L, double tot, V3 hit, V3 nn, V3 lc,
                                                int nl, uint32_t& err) {
   const double area = tot > 0 ? tot : 0.0;
   if (area > 0) {
     nl++;
     const double pw = S.sse_is_two ? area * area : rx_pow(area, S.sse);
-    const V3 lcol = vsc(v3p(L.color), pw / (double)S.n_light);
+    const V3 lcol = vsc(v3p(L.color), light_share(S, pw));
     const V3 ll = vnorm(vsub(v3p(L.pos), hit), err);
     double ldn = vdot(ll, nn);
     if (ldn > 1) ldn = 1.0;
@@ -1582,7 +1640,7 @@ __device__ __forceinline__ void sphere_uv(const SceneDev& S, const Material& m, 
 
 // local_lighting's colour (world_object.rb:51-74) from the light loop's sum lc over nl lit lights, texture filter.
 __device__ __forceinline__ V3 leaf_color(const SceneDev& S, const Material& m, V3 hit, V3 lc, int nl, uint32_t& err) {
-  lc = vdiv(lc, (double)nl);
+  lc = vdiv_lights(S, lc, nl);                     // (callers: nl >= 1 lit lights)
   V3 color;
   if (m.type == OBJ_BOX) {
     color = vadd(vmul(lc, v3p(m.diffuse)), v3p(m.ambient));
@@ -1645,7 +1703,7 @@ RTX_SHADE_FN bool shade_finish(const SceneDev& S, const CameraDev& cam, uint64_t
   if (nl == 0) {
     // WorldObject#path_tracing (world_object.rb:76-90) from hit + delta
     const int pt = cam.pt;
-    const V3 att = vmul(cur.att, vdiv(v3p(m.diffuse), (double)pt));
+    const V3 att = vmul(cur.att, vdiv_count(v3p(m.diffuse), pt));
     V3 left, up;
     pt_basis(n, nn, left, up, err);
     Ray r;
@@ -1737,7 +1795,7 @@ __device__ __forceinline__ bool highlight_leaves_att(const SceneDev& S, const Ra
   for (int l = 0; l < S.n_light; l++) {
     if (!(fired >> l & 1)) continue;
     const RTX_CONST LightDev& L = lights[l];
-    leaf(vdiv(vmul(it.att, vsc(v3(L.color[0], L.color[1], L.color[2]), L.hl_rate)), (double)nfired));
+    leaf(vdiv_lights(S, vmul(it.att, vsc(v3(L.color[0], L.color[1], L.color[2]), L.hl_rate)), nfired));
   }
   return true;
 }
@@ -1786,15 +1844,30 @@ struct ItemPos {
   int px, row, sample;
   bool valid;                      // inside the region (8x8 tiles are padded)
 };
+// CHUNK: the wave's lanes hold the 64 consecutive items of one chunk, k = 64 c +
+// lane.  A tile's 64 pre items are whole chunks, so the tile and its corner are
+// the same for the wave and are computed once, on the scalar unit, from the
+// first active lane's item; only the pixel within the tile and the sample are
+// per lane (shift and mask when pre is a power of two, which is uniform too).
+template <bool CHUNK = false>
 __device__ __forceinline__ ItemPos decode_item(const KParams& p, int k) {
   ItemPos ip;
   if (p.lv_pass == 0) {
     const int tiles_x = (p.nx + 7) >> 3;
-    const int per = 64 * p.pre;
-    const int slot = k / per, r = k - slot * per;
+    const int pre = p.pre, per = 64 * pre;
+    const int kb = CHUNK ? __builtin_amdgcn_readfirstlane(k) & ~63 : k;   // CHUNK: the chunk's first item
+    int slot, l;
+    if ((pre & (pre - 1)) == 0) {               // (uniform) items are never negative: shifts are the divisions
+      const int lp = 31 - __builtin_clz(pre);
+      slot = kb >> (6 + lp);
+      l = (k - slot * per) >> lp;
+    } else {
+      slot = kb / per;
+      l = (k - slot * per) / pre;
+    }
+    const int r = k - slot * per;
     const int tile = p.lv_t0 + slot * p.lv_tstride;
-    const int l = r / p.pre;
-    ip.sample = r - l * p.pre;
+    ip.sample = r - l * pre;
     ip.px = (tile % tiles_x) * 8 + ((l & 1) | ((l >> 1) & 2) | ((l >> 2) & 4));
     ip.row = (tile / tiles_x) * 8 + (((l >> 1) & 1) | ((l >> 2) & 2) | ((l >> 3) & 4));
     ip.valid = ip.px < p.nx && ip.row < p.nrows && row_to_y(p, ip.row) < p.cam->height;

@@ -649,13 +649,15 @@ __device__ __forceinline__ bool lv_walk(const KParams& p, char* lds, bool ext, V
 
 // The ray of a level's queue entry: a camera sample (level 0: `idx` = its
 // item, Camera#lens_func) or the staged child at slot `idx`.  `valid` false
-// for the padding of an 8x8 tile.
+// for the padding of an 8x8 tile.  CHUNK: the wave's active lanes hold consecutive
+// items of one level-0 chunk (the first half of the level kernels), see decode_item.
+template <bool CHUNK = false>
 __device__ __forceinline__ void lv_ray(const KParams& p, int level, uint32_t idx, Item& cur, int& root, int& x, int& y,
                                        int& sample, bool& valid) {
   valid = true;
   if (level == 0) {
     root = (int)idx;
-    const ItemPos ip = decode_item(p, root);
+    const ItemPos ip = decode_item<CHUNK>(p, root);
     x = p.x0 + ip.px;
     y = row_to_y(p, ip.row);
     sample = ip.sample;
@@ -714,7 +716,7 @@ __device__ __forceinline__ void lv_first_half(const KParams& p, char* lds, int l
   bool alive = false;
   if (active) {
     bool valid;
-    lv_ray(p, level, slot, f.cur, f.root, f.x, f.y, f.sample, valid);
+    lv_ray<true>(p, level, slot, f.cur, f.root, f.x, f.y, f.sample, valid);   // (level 0: slot = i, dense)
     if (level == 0) p.lv_redo_of[i] = -1;     // no overflow yet (lv_redo)
     active = valid;                           // tile padding: no record
     alive = valid && (level > 0 || !(depth <= 0 || vr(f.cur.att) < 0.0001));   // rt_map's cutoff (ray_tracer.rb:52)
@@ -826,6 +828,8 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
   uint32_t mask = 0;
   double rate = 0.0;
   bool may_refract = false;
+  double sin_r = 0.0;
+  bool tir = false;
   if (shade) {
     const int cd = depth - 1;
     if (cd > 0 && !(vr(vmul(cur.att, v3p(m->refl_att))) < 0.0001)) mask |= 1u;
@@ -836,10 +840,13 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
       may_refract = true;
       rate = m->rr;
     }
-    if (may_refract && !(sqrt(1.0 - c * c) / rate >= 1) && cd > 0 &&
-        !(vr(vmul(cur.att, v3p(m->refr_att))) < 0.0001))
+    if (may_refract) {                      // refraction()'s sin_r and TIR test, once for the mask and the ray
+      sin_r = refract_sin(c, rate);
+      tir = sin_r >= 1;
+    }
+    if (may_refract && !tir && cd > 0 && !(vr(vmul(cur.att, v3p(m->refr_att))) < 0.0001))
       mask |= 2u;                           // refraction exists (no TIR) and is alive
-    if (nl == 0 && cd > 0 && !(vr(vmul(cur.att, vdiv(v3p(m->diffuse), (double)pt))) < 0.0001))
+    if (nl == 0 && cd > 0 && !(vr(vmul(cur.att, vdiv_count(v3p(m->diffuse), pt))) < 0.0001))
       mask |= ((1u << pt) - 1u) << 2;       // every path-tracing child (same attenuation)
   }
   // Room in the next level: this wave's slice, wave prefix count + one
@@ -862,14 +869,14 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
     // sqrt(s) == 0 iff s == 0), not its direction.  The refraction's test
     // needs the reflected direction, so the reflection is built in full then.
     const bool refr_live = (mask & 2u) != 0;
-    const bool refr_chk = may_refract && !refr_live && !(sqrt(1.0 - c * c) / rate >= 1);   // refraction()'s TIR test
+    const bool refr_chk = may_refract && !refr_live && !tir;
     if ((mask & 1u) || refr_live || refr_chk) {
       refl = reflection(cur.ray, nn, c, hit, delta, errS);
     } else if (vr(vadd(vsc(nn, 2.0 * c * vr(cur.ray.d)), cur.ray.d)) == 0) {
       if (!errS) errS = ERR_ZERO_VEC;
     }
     if (refr_live) {
-      has_refr = refraction(cur.ray, nn, c, hit, refl.d, rate, refr, errS);
+      has_refr = refraction_sin(cur.ray, nn, sin_r, hit, refl.d, refr, errS);
     } else if (refr_chk && vr(vadd(refl.d, cur.ray.d)) == 0) {
       if (!errS) errS = ERR_ZERO_VEC;
     }
@@ -905,7 +912,7 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
       // Skipped when every path-tracing child is cut off: its only raise
       // sites (vertical_vector's zero test, the normalize of a vector with a
       // component 1) cannot fire unless n.normalize raised first (errS).
-      const V3 att = vmul(cur.att, vdiv(v3p(m->diffuse), (double)pt));
+      const V3 att = vmul(cur.att, vdiv_count(v3p(m->diffuse), pt));
       V3 left, up;
       pt_basis(nrm, nn, left, up, errP);
       Ray r;
@@ -1051,7 +1058,7 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
         if (active) {
           bool valid = true;
           if (level == 0) {
-            lv_ray(p, level, slot, cur, root, x, y, sample, valid);
+            lv_ray<true>(p, level, slot, cur, root, x, y, sample, valid);   // (slot = i, dense)
             p.lv_redo_of[i] = -1;
           } else {
             const double2 a = qs[0], b = qs[1], c = qs[2];
@@ -1206,7 +1213,7 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
       if (area > 0) {
         nl++;
         const double pw = S.sse_is_two ? area * area : rx_pow(area, S.sse);
-        const V3 lcol = vsc(v3p(L.color), pw / (double)S.n_light);
+        const V3 lcol = vsc(v3p(L.color), light_share(S, pw));
         const V3 ll = vnorm(vsub(v3p(L.pos), hit), errP);
         double ldn = vdot(ll, nn);
         if (ldn > 1) ldn = 1.0;
@@ -1566,7 +1573,7 @@ __global__ __launch_bounds__(256) void k_tree_finalize(KParams p, int nlev) {
     const int item0 = slot * n_items;
     uint32_t nvis = 0;
     for (int it = (int)threadIdx.x; it < n_items; it += 256) {
-      const ItemPos ip = decode_item(p, item0 + it);
+      const ItemPos ip = decode_item<true>(p, item0 + it);   // (a wave's items: one chunk of the tile)
       if (!ip.valid) continue;
       uint32_t e = 0;
       const V3 c = SD > 16 ? lv_sample(p, base, pex, item0 + it, nlev, lo_p, hi_p, 1, LV_MAXL, e, nvis)

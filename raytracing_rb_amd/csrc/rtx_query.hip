@@ -100,7 +100,7 @@ __global__ __launch_bounds__(LA_BS) void k_lit_area(KParams p, const double* __r
         c = v3(0.0, 0.0, 0.0);
         if (a > 0 && color) {
           const double pw = S.sse_is_two ? a * a : rx_pow(a, S.sse);
-          c = vsc(lcol, pw / (double)S.n_light);
+          c = vsc(lcol, light_share(S, pw));
         }
       }
     }

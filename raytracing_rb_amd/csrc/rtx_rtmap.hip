@@ -242,7 +242,7 @@ __global__ __launch_bounds__(RM_BS) void k_rt_map(KParams p, const double* __res
       if (ls.nl == 0) {
         // WorldObject#path_tracing (world_object.rb:76-90) from hit + delta
         kind = 4;
-        const V3 a = vmul(cur.att, vdiv(v3p(m.diffuse), (double)pt));
+        const V3 a = vmul(cur.att, vdiv_count(v3p(m.diffuse), pt));
         V3 left, up;
         pt_basis(n, nn, left, up, errP);
         Ray r;
