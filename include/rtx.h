@@ -518,7 +518,11 @@ rtx_status rtx_get_option(rtx_context* ctx, const char* key, int64_t* value);
          per-light cube map of the spheres as seen from the light, built at upload: staged in LDS next to the hit
          rings for scenes whose sphere records are staged (sphere mode 3, up to 512 spheres), read from global
          memory beside the 16-bit leaf records of larger scenes (sphere mode 6); 0 = the hierarchy walk; same
-         bits). */
+         bits), read-only "lv_plan_last" (the launch plan of the first fused level launch of the last bounce-level
+         render, recorded by the launcher: bits 0-3 the sphere mode [SphMode, rtx_plan.h], 4-7 the hit ring's
+         fields [0 none, 5 compact, 11 full], 8 the light buffer in LDS, 9 the raise gates in LDS, 10-11 the raise
+         check [0 none, 1 through the buffers, 2 the widened walk], 12 the workgroup's claim counter placed, 16
+         and up the launch's dynamic LDS bytes; -1: no fused launch ran, e.g. lv_split). */
 
 /* ---- Vec3 (fast_4d_matrix.c), pure host functions ------------------------ */
 rtx_vec3   rtx_vec3_from_a(double x, double y, double z);                   /* :75-84   */

@@ -63,10 +63,10 @@ struct rtx_context {
   int* d_work = nullptr;             // ring of per-launch work counters (launches on different streams)
   unsigned work_seq = 0;
   int64_t opt_force_stack = 0;
-  int64_t opt_bvh = 1;               // 0: ordered linear walk; 1: hierarchy from opt_bvh_min spheres; 2: always
+  int64_t opt_bvh = PlanOpts{}.bvh;               // 0: ordered linear walk; 1: hierarchy from opt_bvh_min spheres; 2: always
   int64_t opt_bvh_sah = RTX_BVH_SAH;  // hierarchy splits: 1 binned SAH, 0 median (applies at the next upload)
-  int64_t opt_bvh_min = 32;         // C2 (64 spheres): hierarchy 16.0 ms vs ordered walk 17.8 ms
-  int64_t opt_sphere_src = -1;       // 0: LDS staging (measured faster), 1: scalar loads, 2: nodes LDS + leaves global,
+  int64_t opt_bvh_min = PlanOpts{}.bvh_min;         // C2 (64 spheres): hierarchy 16.0 ms vs ordered walk 17.8 ms
+  int64_t opt_sphere_src = PlanOpts{}.sphere_src;       // 0: LDS staging (measured faster), 1: scalar loads, 2: nodes LDS + leaves global,
                                      // 3: + exact records in LDS, 4: quantized leaves in LDS, -1 auto
   int64_t opt_postpone = -1;         // query_bvh postponing threshold in lanes (-1: auto by hierarchy size)
   int64_t opt_tile_order = -1;       // 1: expensive tiles first (k_tile_cost/k_tile_sort), 0: natural order, -1: auto
@@ -77,17 +77,17 @@ struct rtx_context {
   int64_t opt_lv_stage_pct = 300;    // bounce levels: ray records per staging buffer, % of the batch items
   int64_t opt_lv_rec_pct = 1600;      // bounce levels: tree records of a batch (all levels), % of the batch items
   int64_t opt_lv_floor = 1 << 20;    // bounce levels: at least this many staging and 4x this many tree records
-  int64_t opt_lv_split = 0;          // bounce levels: 1 = three phase launches per level (trace / shadow / shade)
+  int64_t opt_lv_split = PlanOpts{}.lv_split;          // bounce levels: 1 = three phase launches per level (trace / shadow / shade)
   int64_t opt_lv_static = -1;        // bounce levels: % of a launch's chunks scheduled statically (-1 auto)
   int64_t opt_lv_round = -1;         // bounce levels: static chunks in rounds of R per workgroup (0 per wave, -1 auto)
-  int64_t opt_lv_compact = -1;       // bounce levels: 1 = park hits in an LDS ring and shade full waves, -1 auto (when it fits)
+  int64_t opt_lv_compact = PlanOpts{}.lv_compact;       // bounce levels: 1 = park hits in an LDS ring and shade full waves, -1 auto (when it fits)
   int64_t opt_lv_grid_div = 1;       // bounce levels: persistent level grids = resident workgroups / this
   int64_t opt_lv_fin_grid = 0;       // bounce levels: tree reduction blocks per CU (grid-stride over tiles), 0 = one block per tile
   int64_t opt_lv_redo_blocks = 8;    // bounce levels: workgroups of the overflow re-render launch (0: all resident)
   int64_t opt_lv_streams = 2;        // bounce levels: P = the region's tiles in P interleaved parts on P streams at once
   int64_t opt_lv_ray_bytes = 0;      // bounce levels: staged ray record, 0 auto (80 B when every path fits 32 bits), 80, 96
   int64_t opt_lv_hl_cap = 0;         // bounce levels: deferred highlight-check list entries (0 auto)
-  int64_t opt_exact_raises = 1;      // 1 (default): local_lights' shadow walks also check the acos raises of the covers they skip
+  int64_t opt_exact_raises = PlanOpts{}.exact_raises;      // 1 (default): local_lights' shadow walks also check the acos raises of the covers they skip
                                      // (§0.0: C2 +3.7 %, C4 +10.4 % against 0)
   int64_t opt_lv_sort = -1;          // bounce levels: 1 = levels visited bin by bin (direction octant, origin cell), 0 off,
                                      // -1 auto = on
@@ -95,10 +95,11 @@ struct rtx_context {
                                      // 307 ms), else the last level only (C2 4.60 -> 4.57 ms; all levels 4.65 -> 4.88, r10d/r10k)
   int64_t opt_lv_sort_bits = 0;      // bounce levels: 2^bits origin cells per axis (3 or 4); 0 auto: 4 above 512 spheres, else 3
   int64_t opt_lv_sort_copy = 0;      // bounce levels: 1 = binning copies the rays' records into bin order (r11i: C4 296 -> 342 ms, off)
-  int64_t opt_lbuf = 1;              // bounce levels: 1 = shadow walks through the light buffer where it is staged (§3.18)
+  int64_t opt_lbuf = PlanOpts{}.lbuf;              // bounce levels: 1 = shadow walks through the light buffer where it is staged (§3.18)
   int n_cus = 0;                     // compute units of the device (hipDeviceAttributeMultiprocessorCount)
   unsigned long long* d_lvstats = nullptr;   // rtx_level_stats of the last bounce-level render call
   int64_t last_sort_levels = 0;              // levels per batch the last bounce-level render binned (lv_sort_last)
+  int64_t last_plan = -1;                    // rtx_plan.h pack_plan of its first fused level launch, -1 none (lv_plan_last)
   uint32_t* d_tile_rays = nullptr;   // rtx_tile_rays: rays per 8x8 tile of the last whole-frame level render
   size_t tile_rays_n = 0;
   int32_t* d_rowtiles = nullptr;     // rtx_render_tile_list_device: the tile list on the device
@@ -247,6 +248,10 @@ rtx_status rtx_get_option(rtx_context* c, const char* key, int64_t* value) {
   }
   if (!strcmp(key, "lv_sort_last")) {         // read-only: levels per batch the last bounce-level render binned
     *value = c->last_sort_levels;
+    return RTX_OK;
+  }
+  if (!strcmp(key, "lv_plan_last")) {         // read-only: the launch plan of the last bounce-level render's first
+    *value = c->last_plan;                    // fused level launch, as the launcher recorded it (-1: none ran)
     return RTX_OK;
   }
   if (!strcmp(key, "lv_sort_effective")) {    // read-only: whether the next whole-frame bounce-level render bins its levels
@@ -527,14 +532,7 @@ static int required_stack(const rtx_context* c) {
 // Sphere walk of the next launch (SphMode); the launchers fall back to scalar
 // loads when the records exceed the LDS budget.
 static int sph_mode(const rtx_context* c) {
-  const bool bvh = c->opt_bvh == 2 || (c->opt_bvh == 1 && c->scene.n_sphere >= c->opt_bvh_min);
-  if (bvh && c->scene.bvh_root != BVH_NONE)
-    return c->opt_sphere_src == 4   ? SPH_BVH_QLDS
-           : c->opt_sphere_src == 3 ? SPH_BVH_LDSX
-           : c->opt_sphere_src == 2 ? SPH_BVH_MIX
-           : c->opt_sphere_src == 1 ? SPH_BVH_GLOBAL
-                                    : SPH_BVH_LDS;
-  return c->opt_sphere_src == 1 ? SPH_LIN_SCALAR : SPH_LIN_LDS;
+  return sph_mode_of(c->scene, (int)c->opt_bvh, (int)c->opt_bvh_min, (int)c->opt_sphere_src);   // (rtx_plan.h)
 }
 
 // Global per-lane regions (ray-stack entries beyond LDS) for every lane a persistent launch can keep resident (512 per CU at
@@ -684,6 +682,7 @@ static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_
   const int sort_from = lv_sort_from(c, n0);
   const bool sort = sort_from > 0;
   c->last_sort_levels = sort ? std::max(0, c->cam.depth - sort_from) : 0;   // (read-only option lv_sort_last)
+  c->last_plan = -1;                           // (read-only option lv_plan_last: set by the first fused launch)
   const size_t sz_key = sort ? al256(scap * 2) : 0, sz_perm = sort ? al256(scap * 8) : 0,
                sz_bins = sort ? al256((size_t)LV_BINS * 8) : 0;
   // One buffer set per part: with lv_streams = P the region's tiles are
@@ -784,7 +783,7 @@ static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_
                                                               (int)c->opt_lv_split)
                                            : sph_mode(c);
   const hipError_t e = launch_levels(p, mode, maxs, std::max(1, c->cam.depth), batch_tiles, stream,
-                                     c->opt_kernel_events ? &kev : nullptr, parts > 1 ? &aux : nullptr);
+                                     c->opt_kernel_events ? &kev : nullptr, parts > 1 ? &aux : nullptr, &c->last_plan);
   if (c->opt_kernel_events) c->n_ev = kev.n;
   const hipError_t f = hipFreeAsync(buf, stream);
   HIPCHK(c, e);

@@ -1508,7 +1508,6 @@ RTX_SHADE_FN void hit_info(const SceneDev& S, int obj, const Ray& ray, V3& hit, 
 // conflict-free); deeper entries go to the lane's own contiguous region of a
 // global buffer (12 doubles per entry: one push or pop touches two 64-B lines,
 // where a private-array entry, swizzled across the wave, touched 21).
-constexpr int ITEM_WORDS = 11;
 constexpr int GITEM_DOUBLES = 12;
 struct Stack {
   int n;
@@ -1883,59 +1882,22 @@ __device__ __forceinline__ ItemPos decode_item(const KParams& p, int k) {
   return ip;
 }
 
-// LDS budgets.  Linear walk: 16 B per sphere in 256-thread workgroups, small
-// enough for several workgroups per CU.  Hierarchy: nodes + leaf records in
-// one 512-thread workgroup per CU (2 waves per SIMD, the register-limited
-// occupancy), next to its stacks and cover lists.
-constexpr size_t LDS_SPHERE_BYTES = 32 * 1024;
-constexpr size_t LDS_LIN_BLOCK_BYTES = 76 * 1024;   // two 256-thread workgroups per CU
-constexpr int BS_LIN = 256;                         // (LDS_TOTAL_BYTES, BS_BVH: rtx_scene.h)
+// (LDS budgets, BS_LIN, ITEM_WORDS: rtx_plan.h)
 #ifndef RTX_WPS
 #define RTX_WPS 2            // waves per SIMD the kernels are compiled for (256 VGPRs)
 #endif
 
-// Fills the LDS layout of `p` for `mode` and returns the dynamic LDS bytes.
+// Fills the LDS layout of `p` for `mode` (rtx_plan.h walk_lds) and returns the dynamic LDS bytes.
+inline size_t apply_walk_lds(KParams& p, const WalkLds& w) {
+  if (w.leaf >= 0) p.lds_leaf = w.leaf;        // (modes that stage no hierarchy never read it)
+  p.lds_stack = w.stack, p.lds_cov = w.cov, p.lds_items = w.items;
+  p.lds_x64 = w.x64, p.lds_xobj = w.xobj, p.lds_mat = w.mat, p.lds_sphr = w.sphr;
+  p.lds_lbuf = p.lds_rgate = -1;
+  p.stk_slots = w.stk_slots;
+  return w.bytes;
+}
 inline size_t lds_layout(KParams& p, int mode, int bs) {
-  const SceneDev& S = p.scene;
-  size_t off = 0;
-  if (mode == SPH_LIN_LDS) off = (size_t)(S.n_sphere + 4) * 16;
-  p.lds_x64 = p.lds_xobj = p.lds_mat = p.lds_sphr = p.lds_lbuf = p.lds_rgate = -1;
-  if (mode == SPH_BVH_LDS || mode == SPH_BVH_MIX || mode == SPH_BVH_LDSX || mode == SPH_BVH_QLDS) {
-    off = (size_t)S.n_nodes * sizeof(Bvh4Node);
-    p.lds_leaf = (int32_t)off;
-    if (mode == SPH_BVH_QLDS) off += (size_t)S.n_slots * 8;   // 16-bit records
-    else if (mode != SPH_BVH_MIX) off += (size_t)S.n_slots * 16;
-    if (mode == SPH_BVH_LDSX) {
-      p.lds_x64 = (int32_t)off;
-      off += (size_t)S.n_slots * sizeof(Sphere64);
-      p.lds_xobj = (int32_t)off;
-      off += (size_t)S.n_slots * 4;
-      off = (off + 15) & ~(size_t)15;
-      p.lds_mat = (int32_t)off;                 // shading's material and sphere record of the hit object
-      off += (size_t)S.n_obj * sizeof(Material);
-      p.lds_sphr = (int32_t)off;
-      off += (size_t)S.n_sphere * sizeof(Sphere64);
-    }
-  }
-  off = (off + 15) & ~(size_t)15;
-  p.lds_stack = (int32_t)off;
-  p.lds_cov = (int32_t)off;
-  if (sph_is_bvh(mode)) {
-    off += (size_t)S.bvh_stack * bs * (mode == SPH_BVH_QLDS ? 2 : 4);   // QLDS: int16 entries
-    off = (off + 15) & ~(size_t)15;
-    p.lds_cov = (int32_t)off;
-    off += (size_t)COVER_K * bs * 12;
-  }
-  // the bottom of every lane's ray stack, as many entries as fit the budget
-  off = (off + 15) & ~(size_t)15;
-  p.lds_items = (int32_t)off;
-  const size_t budget = sph_is_bvh(mode) ? LDS_TOTAL_BYTES : LDS_LIN_BLOCK_BYTES;
-  const size_t per = (size_t)ITEM_WORDS * 8 * bs;
-  int slots = budget > off ? (int)((budget - off) / per) : 0;
-  if (slots > p.stk_slots_max) slots = p.stk_slots_max;
-  p.stk_slots = slots;
-  off += (size_t)slots * per;
-  return off;
+  return apply_walk_lds(p, walk_lds(p.scene, mode, bs, p.stk_slots_max));
 }
 
 }  // namespace rtx

@@ -679,31 +679,6 @@ int stack_bucket(int need) {
 }
 
 
-int resolve_mode(const SceneDev& S, int mode) {
-  if (mode == SPH_BVH_QLDS) {                  // nodes + 16-bit leaf records + 16-bit stacks, when conservative
-    const size_t need = (size_t)S.n_nodes * sizeof(Bvh4Node) + (size_t)S.n_slots * 8 +
-                        (size_t)S.bvh_stack * BS_BVH * 2 + (size_t)COVER_K * BS_BVH * 12 + 64;
-    if (S.q_ok && need <= LDS_TOTAL_BYTES) return mode;
-    mode = SPH_BVH_MIX;
-  }
-  if (mode == SPH_BVH_LDSX) {                  // the staged hierarchy plus its exact records
-    const size_t need = bvh_lds_bytes(S.n_nodes, S.n_slots, S.bvh_stack) + (size_t)S.n_slots * (sizeof(Sphere64) + 4) +
-                        16 + (size_t)S.n_obj * sizeof(Material) + (size_t)S.n_sphere * sizeof(Sphere64);
-    if (need <= LDS_TOTAL_BYTES) return mode;
-    mode = SPH_BVH_LDS;
-  }
-  if (mode == SPH_BVH_MIX) {                   // nodes in LDS, leaves global: needs room for the nodes
-    const size_t need = (size_t)S.n_nodes * sizeof(Bvh4Node) + (size_t)S.bvh_stack * BS_BVH * 4 +
-                        (size_t)COVER_K * BS_BVH * 12 + 64;
-    return need > LDS_TOTAL_BYTES ? SPH_BVH_GLOBAL : SPH_BVH_MIX;
-  }
-  if (mode == SPH_LIN_LDS && (size_t)(S.n_sphere + 4) * 16 > LDS_SPHERE_BYTES) return SPH_LIN_SCALAR;
-  if (mode == SPH_BVH_LDS && bvh_lds_bytes(S.n_nodes, S.n_slots, S.bvh_stack) > LDS_TOTAL_BYTES)
-    return SPH_BVH_GLOBAL;
-  return mode;
-}
-
-
 static thread_local KernelEvents* g_kev = nullptr;   // set by launch_render for its launches
 static thread_local bool g_work_zeroed = false;      // launch_one: the work counter is already zero
 

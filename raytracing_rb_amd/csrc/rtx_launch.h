@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rtx_plan.h"
 #include "rtx_scene.h"
 
 namespace rtx {
@@ -135,28 +136,7 @@ struct KParams {
   uint32_t* lv_bins;               // LV_BINS counts, LV_BINS cursors (the first 8 << 3 lv_cell_bits used)
 };
 
-// Where the sphere walk reads its records:
-enum SphMode : int {
-  SPH_LIN_LDS = 0,       // ordered linear walk, float32 pre-test records staged in LDS
-  SPH_LIN_SCALAR = 1,    // ordered linear walk, records by scalar loads
-  SPH_BVH_LDS = 2,       // four-wide ball hierarchy, nodes + leaf records staged in LDS
-  SPH_BVH_GLOBAL = 3,    // four-wide ball hierarchy, nodes + leaf records by scalar loads
-  SPH_BVH_MIX = 4,       // four-wide ball hierarchy, nodes staged in LDS, leaf records from global memory
-                         // (bounce-level engine only: room for the hit rings of k_level_c; the lanes
-                         // engine walks it as SPH_BVH_LDS)
-  SPH_BVH_LDSX = 5,      // as SPH_BVH_LDS, and the binary64 sphere records of the exact test with their
-                         // object indices staged too (bounce-level engine only, small hierarchies: no
-                         // global load inside the walk; the lanes engine walks it as SPH_BVH_LDS)
-  SPH_BVH_QLDS = 6,      // four-wide ball hierarchy, nodes + 16-bit quantized leaf records (SceneDev::bvh_q)
-                         // in LDS, 16-bit traversal stacks (bounce-level engine only, hierarchies too big for
-                         // SPH_BVH_LDS next to a hit ring, e.g. C4; the lanes engine walks it as SPH_BVH_LDS)
-};
-
-
-// Sphere modes that walk the ball hierarchy.
-constexpr bool sph_is_bvh(int m) {
-  return m == SPH_BVH_LDS || m == SPH_BVH_GLOBAL || m == SPH_BVH_MIX || m == SPH_BVH_LDSX || m == SPH_BVH_QLDS;
-}
+// (SphMode, sph_is_bvh, levels_auto_mode, resolve_mode and the level launch plan: rtx_plan.h, host-only)
 
 // HIP event pairs recorded on the launch stream around every ray-tree kernel
 // launch of one render call (option "kernel_events", rtx_kernel_time).
@@ -170,8 +150,7 @@ int stack_bucket(int need);
 // per (kernel, block size, dynamic LDS bytes, device); raises the kernel's
 // dynamic-LDS limit on first use.
 hipError_t launch_fit(const void* kern, int bs, size_t lds, int& cus, int& per_cu);
-// mode: SphMode; a linear mode whose records exceed the LDS budget falls back to
-// SPH_LIN_SCALAR, a BVH mode to SPH_BVH_GLOBAL.  Counting launches always walk
+// mode: SphMode, resolved by rtx_plan.h resolve_mode.  Counting launches always walk
 // linearly (the counters are the reference's brute-force events).
 hipError_t launch_render(KParams p, int mode, bool count, int maxs, hipStream_t s, KernelEvents* kev = nullptr);
 hipError_t launch_trace(KParams p, int mode, int maxs, hipStream_t s);
@@ -196,23 +175,17 @@ struct LvAux {
   hipEvent_t ev_first, ev_done[LV_MAX_PARTS - 1];
 };
 hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tiles, hipStream_t s,
-                         KernelEvents* kev = nullptr, const LvAux* aux = nullptr);
+                         KernelEvents* kev = nullptr, const LvAux* aux = nullptr, int64_t* plan_out = nullptr);
+// (plan_out: receives rtx_plan.h pack_plan of the call's first fused level launch, as launched)
 // Tree-record bytes for a scene with n_light lights (one leaf per fired light).
 int levels_rec_bytes(int n_light);
-// The bounce-level engine's sphere mode for sphere_src auto: SPH_BVH_LDSX
-// when the hierarchy, its exact records and the full hit ring fit LDS (C2);
-// SPH_BVH_MIX when the staged hierarchy leaves no LDS for a hit ring while
-// the hierarchy's nodes alone with the compact ring fit (C4); else SPH_BVH_LDS.
-int levels_auto_mode(const SceneDev& S, int mode, int compact, int split);
 constexpr size_t RAY_BYTES = 96;                // staged ray record of the bounce-level engine (at most)
 constexpr size_t LV_HIT_BYTES = 64;             // split phases: hit-queue record
-constexpr int LV_SPLIT_MAX_LIGHTS = 16;         // split phases only up to this many lights (shadow results per hit)
 hipError_t launch_path_trace(KParams p, hipStream_t s);
 // The lanes engine's re-render of the level-0 items listed in lv_redo_list
 // (SRC_LIST; exits at once when the list is empty).
 hipError_t launch_redo(const KParams& q, int mode, int maxs, int n, hipStream_t s);
 int read_level_stamps(unsigned long long* out, int reset);   // diagnostic builds
-int resolve_mode(const SceneDev& S, int mode);   // (its budget: rtx_scene.h bvh_lds_bytes / bvh_lds_budget)
 hipError_t launch_quantize(const double* rgb, int w, int h, size_t stride, int blend, uint8_t* out,
                            hipStream_t s);
 // Rank-major packed tiles (n ranks x rows_per_rank rows x w x 3) -> frame rows.

@@ -569,7 +569,7 @@ __device__ __forceinline__ void lv_stage_scene(const KParams& p, float4* lds_sph
 // walk), XR_WALK with the hierarchy walk widened to the light's cone; XR_NONE
 // not.  A kernel variant each (the launcher picks XR_BUF where both buffers
 // are in place): the widened walk's registers would cost XR_BUF's kernels.
-enum { XR_NONE = 0, XR_BUF = 1, XR_WALK = 2 };
+// (XR_NONE / XR_BUF / XR_WALK: rtx_plan.h)
 template <int SPH, int BS>
 __device__ __forceinline__ bool lv_walk(const KParams& p, char* lds, bool ext, V3 o, V3 d, V3 L, double rad,
                                         double& best, int& besti, V3& hit, bool& hin, double& total, uint32_t& err,
@@ -1007,11 +1007,7 @@ __global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level(KParams p, int level)
 // walk's LDS (C4's hierarchy): the second half then re-derives the ray's
 // origin and direction, the same bits either way (level >= 1: reloaded from
 // the queue; level 0: Camera#lens_func re-evaluated for the item's key).
-constexpr int LV_RING = 128;
-constexpr int LV_RING_FIELDS = 11;
-constexpr int LV_RING_FIELDS_SMALL = 5;
-constexpr size_t LV_RING_WAVE_BYTES = (size_t)LV_RING * LV_RING_FIELDS * 8;
-constexpr size_t LV_RING_WAVE_BYTES_SMALL = (size_t)LV_RING * LV_RING_FIELDS_SMALL * 8;
+// (LV_RING, LV_RING_FIELDS, LV_RING_FIELDS_SMALL and the rings' bytes per wave: rtx_plan.h)
 
 template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
 __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
@@ -1902,25 +1898,6 @@ int read_level_stamps(unsigned long long* out, int reset) {
   return 0;
 }
 
-int levels_auto_mode(const SceneDev& S, int mode, int compact, int split) {
-  if (mode != SPH_BVH_LDS || compact == 0 || split) return mode;
-  const size_t waves = BS_BVH / 64;
-  const size_t walk = (size_t)S.bvh_stack * BS_BVH * 4 + (size_t)COVER_K * BS_BVH * 12 + 64;
-  const size_t nodes = (size_t)S.n_nodes * sizeof(Bvh4Node), leaves = (size_t)S.n_slots * 16;
-  const size_t exact = (size_t)S.n_slots * (sizeof(Sphere64) + 4) + 16 + (size_t)S.n_obj * sizeof(Material) +
-                       (size_t)S.n_sphere * sizeof(Sphere64);   // + shading's materials and sphere records
-  // C2: the exact test's records staged too (r05d: 4.91-4.94 -> 4.85 ms, same bits)
-  if (nodes + leaves + exact + walk + waves * LV_RING_WAVE_BYTES <= LDS_TOTAL_BYTES) return SPH_BVH_LDSX;
-  if (nodes + leaves + walk + waves * LV_RING_WAVE_BYTES <= LDS_TOTAL_BYTES) return mode;   // LDS + full ring
-  if (nodes + leaves + walk + waves * LV_RING_WAVE_BYTES_SMALL <= LDS_TOTAL_BYTES) return mode;   // + compact ring
-  // C4: the leaves as 16-bit records, 16-bit stacks (+ alignment)
-  const size_t walk16 = (size_t)S.bvh_stack * BS_BVH * 2 + (size_t)COVER_K * BS_BVH * 12 + 64;
-  if (S.q_ok && nodes + (size_t)S.n_slots * 8 + walk16 + 32 + waves * LV_RING_WAVE_BYTES_SMALL <= LDS_TOTAL_BYTES)
-    return SPH_BVH_QLDS;
-  if (nodes + walk + waves * LV_RING_WAVE_BYTES_SMALL <= LDS_TOTAL_BYTES) return SPH_BVH_MIX;
-  return mode;
-}
-
 extern "C" int rtxdbg_read_walkstats(unsigned long long* out, int reset) {   // diagnostic builds (levels unit)
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rtx_walkstats), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
   if (reset) {
@@ -1988,6 +1965,8 @@ static void (*level_c_kernel(bool last, int xrm, bool sort))(KParams, int) {
   return level_c_xr<SPH, BS, RF, false, false>(xrm);
 }
 
+static thread_local int64_t* g_plan_out = nullptr;   // set by launch_levels for its first fused launch
+
 #ifndef RTX_LV_FUSED_BS
 #define RTX_LV_FUSED_BS 0                  // k_level's block size (0: BS_LIN / BS_BVH)
 #endif
@@ -2001,72 +1980,30 @@ static hipError_t launch_level_bs(const KParams& p, int kind, int level, long ca
                                   KernelEvents* kev) {
   KParams q = p;
   q.stk_slots_max = 0;                         // no ray stack in this engine
-  size_t lds = lds_layout(q, SPH, BS);
-  // exact_raises (the default) compiles the shadow walks' raise check in (k_level / k_level_c <..., XR>):
-  // XR_BUF through the light and raise buffers where both serve this launch (the LDS-staged light
-  // buffer of SPH_BVH_LDSX, the global one of SPH_BVH_QLDS), else XR_WALK; exact_raises = 0: XR_NONE
-  const bool xr = q.exact_raises != 0;
-  bool bufs = false;                           // (SPH_BVH_LDSX: settled below, once the rings are placed)
-  if constexpr (SPH == SPH_BVH_QLDS) bufs = q.lv_lbuf && q.scene.lbuf && q.scene.rbuf;
-  int xrm = !xr ? XR_NONE : bufs ? XR_BUF : XR_WALK;
+  // the launch plan (rtx_plan.h level_plan): the hit ring, the light buffer and the raise gates in LDS,
+  // the raise check's variant, the workgroup's claim counter and the dynamic LDS bytes
+  const PlanIn in{q.lv_compact, q.lv_lbuf, q.exact_raises, q.scene.lbuf != nullptr, q.scene.rbuf != nullptr};
+  const LevelPlan pl = level_plan(q.scene, in, SPH, BS, BS == fused_bs<SPH>(), kind);
+  apply_walk_lds(q, pl.walk);
+  const size_t lds = pl.lds;
+  if (pl.ring_fields) q.lds_ring = pl.lds_ring;
+  q.lds_lbuf = pl.lds_lbuf;
+  q.lds_rgate = pl.lds_rgate;
+  if (pl.lds_sched >= 0) q.lds_sched = pl.lds_sched;
+  else q.lv_round = 0;                         // no room for the counter: the per-wave static schedule
+  const int xrm = pl.xrm;
+  // k_level_c (hit compaction) is instantiated for the fused kernel's block size only; XR_BUF only for
+  // the sphere modes with a light buffer (level_c_xr)
   auto kern = kind == 0 ? (xrm == XR_NONE ? k_level<SPH, BS, XR_NONE> : k_level<SPH, BS, XR_WALK>)
               : kind == 1 ? k_lv_trace<SPH, BS> : k_lv_shadow<SPH, BS>;
-  // hit compaction when the rings fit next to the walk's LDS (k_level_c is
-  // instantiated for the fused kernel's block size only)
-  int ring_fields = 0;
-  if constexpr (BS == fused_bs<SPH>()) if (kind == 0 && q.lv_compact != 0) {
-    constexpr bool BVH = sph_is_bvh(SPH);
-    const size_t ring = (lds + 15) & ~(size_t)15, budget = BVH ? LDS_TOTAL_BYTES : LDS_LIN_BLOCK_BYTES;
-    const size_t need = ring + (size_t)(BS / 64) * LV_RING_WAVE_BYTES;
-    const size_t need_small = ring + (size_t)(BS / 64) * LV_RING_WAVE_BYTES_SMALL;
-    if (need <= budget && q.lv_compact != 2) { // the full ring
-      q.lds_ring = (int32_t)ring;
-      lds = need;
-      ring_fields = LV_RING_FIELDS;
-    } else if (BVH && need_small <= budget) {  // the compact ring (C4-sized hierarchies)
-      q.lds_ring = (int32_t)ring;
-      lds = need_small;
-      ring_fields = LV_RING_FIELDS_SMALL;
-    }
-  }
-  // the light buffer (§3.18) after the rings, when it fits: the shadow walks read their cell's leaves;
-  // with exact_raises the raise buffer's gates after it (§2.4), in LDS when they fit too
-  if constexpr (SPH == SPH_BVH_LDSX) if (kind == 0 && q.lv_lbuf && q.scene.lbuf) {
-    const size_t at = (lds + 15) & ~(size_t)15, bytes = (size_t)q.scene.lbuf_stride * q.scene.n_light * 2;
-    if (at + bytes <= LDS_TOTAL_BYTES) {
-      q.lds_lbuf = (int32_t)at;
-      lds = at + bytes;
-      if (xr && q.scene.rbuf) {
-        xrm = XR_BUF;
-        const size_t ga = (lds + 15) & ~(size_t)15, gb = (size_t)q.scene.rgate_stride * q.scene.n_light * 2;
-        if (ga + gb <= LDS_TOTAL_BYTES) {
-          q.lds_rgate = (int32_t)ga;
-          lds = ga + gb;
-        }
-      }
-    }
-  }
   if constexpr (BS == fused_bs<SPH>()) {
     const bool last = level == q.lv_last_level, sort = q.lv_sort && level + 1 >= q.lv_sort;
-    if (ring_fields == LV_RING_FIELDS) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS>(last, xrm, sort);
-    else if (ring_fields == LV_RING_FIELDS_SMALL) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS_SMALL>(last, xrm, sort);
-    else if (kind == 0 && xrm == XR_BUF) {     // (no ring: k_level, which walks the widened hierarchy)
-      xrm = XR_WALK;
-      q.lds_lbuf = q.lds_rgate = -1;
-      kern = k_level<SPH, BS, XR_WALK>;
-    }
+    if (pl.ring_fields == LV_RING_FIELDS) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS>(last, xrm, sort);
+    else if (pl.ring_fields == LV_RING_FIELDS_SMALL) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS_SMALL>(last, xrm, sort);
   }
-  // rounds (lv_round): the workgroup's claim counter after everything else; where the layout leaves no
-  // room for it, this launch keeps the per-wave static schedule (placed whatever lv_round is: a kernel's
-  // dynamic LDS size, which launch_fit caches and raises the kernel's limit to, does not depend on the option)
-  {
-    const size_t at = (lds + 3) & ~(size_t)3;
-    if (at + 4 <= (sph_is_bvh(SPH) ? LDS_TOTAL_BYTES : LDS_LIN_BLOCK_BYTES)) {
-      q.lds_sched = (int32_t)at;
-      lds = at + 4;
-    } else {
-      q.lv_round = 0;
-    }
+  if (kind == 0 && g_plan_out) {               // (launch_levels: the call's first fused launch, as launched)
+    *g_plan_out = pack_plan(pl);
+    g_plan_out = nullptr;
   }
   int cus = 0, per_cu = 0;                     // (also raises the kernel's dynamic-LDS limit once)
   const hipError_t e = cus_and_fit(reinterpret_cast<const void*>(kern), BS, lds, cus, per_cu);
@@ -2223,9 +2160,13 @@ static hipError_t level_batch(KParams q, int mode, int maxs, int nlev, int n0_ma
 }
 
 hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tiles, hipStream_t s,
-                         KernelEvents* kev, const LvAux* aux) {
+                         KernelEvents* kev, const LvAux* aux, int64_t* plan_out) {
   const int tiles = ((p.nx + 7) / 8) * ((p.nrows + 7) / 8);
   if (tiles == 0) return hipSuccess;
+  struct PlanScope {                           // (cleared on every way out: a call of split phases records none)
+    explicit PlanScope(int64_t* o) { g_plan_out = o; }
+    ~PlanScope() { g_plan_out = nullptr; }
+  } plan_scope(plan_out);
   mode = resolve_mode(p.scene, mode);
   batch_tiles = std::max(1, std::min(batch_tiles, tiles));
   const int per_tile = 64 * p.pre;

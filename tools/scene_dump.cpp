@@ -6,9 +6,17 @@
 //
 //   g++ -O2 -std=c++17 -ffp-contract=off -o scene_dump tools/scene_dump.cpp -lz -lpthread
 //   scene_dump scenes/c2_world.yml [sah: 1 (default) or 0]
+//
+// scene_dump --plan world.yml...: instead, per world, one line "plan <packed plan>
+// <name> <value> ..." with the launch plan of its fused level launches under default
+// options (rtx_plan.h fused_plan, the arithmetic the launcher runs; the read-only option
+// lv_plan_last reports the same integer after a render) and the scalars it depends on;
+// "status <code> <message>" for a world the host build refuses (tests/test_level_plans.py).
 #include <stdio.h>
+#include <string.h>
 
 #include "../raytracing_rb_amd/cli/scene_load.hpp"
+#include "../raytracing_rb_amd/csrc/rtx_plan.h"
 #include "../raytracing_rb_amd/csrc/rtx_scene_build.h"
 
 using namespace rtx;
@@ -25,11 +33,34 @@ static void array(const char* name, const std::vector<T>& v) {
   printf("array %s %zu %016llx\n", name, v.size() * sizeof(T), (unsigned long long)fnv1a(v.data(), v.size() * sizeof(T)));
 }
 
+static int plans(int n, char** worlds) {
+  for (int k = 0; k < n; k++) {
+    rtxcli::Scene sc;
+    rtxcli::load_world(worlds[k], sc);
+    HostScene H;
+    std::string msg;
+    const rtx_status st = build_host_scene(&sc.desc, true, H, msg);
+    if (st != RTX_OK) {
+      printf("status %d %s\n", (int)st, msg.c_str());
+      continue;
+    }
+    const SceneDev& S = H.dev;
+    printf("plan %lld", (long long)fused_plan(S, PlanOpts{}));
+#define I(f) printf(" " #f " %d", (int)S.f)
+    I(n_sphere), I(n_light), I(n_obj), I(n_nodes), I(n_slots), I(bvh_stack), I(q_ok);
+    I(lbuf_n), I(lbuf_stride), I(rbuf_n), I(rgate_stride), I(rbuf_sphere);
+#undef I
+    printf("\n");
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s world.yml [sah]\n", argv[0]);
+    fprintf(stderr, "usage: %s world.yml [sah] | --plan world.yml...\n", argv[0]);
     return 2;
   }
+  if (!strcmp(argv[1], "--plan")) return plans(argc - 2, argv + 2);
   rtxcli::Scene sc;
   rtxcli::load_world(argv[1], sc);
   HostScene H;
