@@ -136,7 +136,7 @@ typedef struct rtx_camera_desc {
   int32_t pre_sample_times;
   int32_t max_sample_times;
   int32_t trace_depth;
-  int32_t monte_carlo_diffusion_times;
+  int32_t monte_carlo_diffusion_times;   /* >= 0; 0: an unlit hit makes no path-tracing child (plain Whitted) */
 } rtx_camera_desc;
 
 /* Vec3 value with its cached norm, as Vec3Type (fast_4d_matrix.c:57-60). */
@@ -448,8 +448,11 @@ rtx_status rtx_level_stats(rtx_context* ctx, int64_t* out, int32_t n);
 rtx_status rtx_set_option(rtx_context* ctx, const char* key, int64_t value);
 rtx_status rtx_get_option(rtx_context* ctx, const char* key, int64_t* value);
 /* read-only key: "engine_effective" (the engine the next render of the uploaded scene and camera runs:
-         "engine", except that the bounce-level engine falls back to the lanes engine for trace_depth > 64,
-         monte_carlo_diffusion_times > 14 or more than 255 lights), "lv_ray_bytes_effective" (80 or 96: the
+         "engine", except that the bounce-level engine falls back to the lanes engine for
+         monte_carlo_diffusion_times > 14 (a scene holds at most 32 lights, rtx_scene_upload refuses more, so
+         its limit of 255 lights, the leaf count of a tree record, is never met); a camera whose ray stack
+         1 + (trace_depth - 1) * (1 + monte_carlo_diffusion_times) exceeds 64 entries, every trace_depth > 64
+         among them, is rendered by neither engine: RTX_EINVAL), "lv_ray_bytes_effective" (80 or 96: the
          staged ray record of the next bounce-level render), "sph_mode_effective" (where the next bounce-level
          render's walks read the spheres: 0 linear walk, records in LDS; 1 linear, scalar loads; 2 hierarchy in
          LDS; 3 hierarchy by scalar loads; 4 nodes in LDS, leaf records global; 5 hierarchy and exact records in
@@ -464,7 +467,9 @@ rtx_status rtx_get_option(rtx_context* ctx, const char* key, int64_t* value);
          hit ring fit LDS, 0 when the hierarchy and a hit ring do, else 4 when that and the compact hit ring fit,
          else 2 when the nodes and the compact ring fit, else 0;
          every choice renders the same bits), "lds_stack" (ray-stack entries per lane kept in LDS,
-         -1 = as many as fit), "force_stack" (per-lane ray-stack bucket), "postpone" (hierarchy walks
+         -1 = as many as fit), "force_stack" (lanes engine: ray-stack entries per lane, rounded up to 8, 16, 32 or
+         64, 0 [default] = the camera's need 1 + (trace_depth - 1) * (1 + monte_carlo_diffusion_times); [0, 64]; a
+         value whose bucket is below the need fails the render with RTX_EINVAL; same bits), "postpone" (hierarchy walks
          still running in fewer lanes of a wave than this are postponed; -1 [default] = 16 from 64 nodes, 0 never), "tile_order" (1 expensive
          8x8 tiles first by a primary-hit probe, 0 row-major, -1 [default] = 1 up to 512 spheres; the order
          changes no bit), "kernel_events" (1: time the ray-tree launches, rtx_kernel_time),

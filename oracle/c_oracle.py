@@ -38,6 +38,9 @@ def lib():
         L.rto_render_pixels.restype = C.c_int
         L.rto_render_pixels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+        L.rto_tree_stats.restype = C.c_int
+        L.rto_tree_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p]
         L.rto_trace.restype = C.c_int
         L.rto_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                 C.c_void_p]
@@ -87,6 +90,20 @@ class Oracle:
         if counts:
             return out, st, rc, cnt
         return out, st, rc
+
+    def tree_stats(self, xy=None, seed=1):
+        """(max_pending int32 [n], rays per tree level int64 [trace_depth], status int32 [n], rc) of the
+        pixels xy (None: the frame, x outer): rto_tree_stats."""
+        if xy is None:
+            xy = [(x, y) for x in range(self.camera.width) for y in range(self.camera.height)]
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        pend = np.zeros(len(xy), np.int32)
+        st = np.zeros(len(xy), np.int32)
+        nlev = max(int(self.camera.trace_depth), 1)
+        levels = np.zeros(nlev, np.uint64)
+        rc = lib().rto_tree_stats(self.h, len(xy), xy.ctypes.data, seed, pend.ctypes.data, levels.ctypes.data, nlev,
+                                  st.ctypes.data)
+        return pend, levels.astype(np.int64), st, rc
 
     def trace(self, rays, keys, seed=1):
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)

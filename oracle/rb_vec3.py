@@ -28,6 +28,19 @@ class RtxError(Exception):
         self.kind = kind
 
 
+def fdiv(a, b):
+    """a / b as the C extension divides (a plain C division, ``:209-224``): IEEE
+    binary64, so a zero divisor gives +-inf, or NaN for 0 / 0 and NaN / 0, where
+    Python raises ZeroDivisionError.  The one case the hot path reaches is
+    ``diffuse_rate / pt_times.to_f`` with monte_carlo_diffusion_times 0
+    (world_object.rb:78)."""
+    if b == 0.0:
+        if a != a or a == 0.0:
+            return math.nan
+        return math.copysign(math.inf, a) * math.copysign(1.0, b)
+    return a / b
+
+
 class Vec3:
     __slots__ = ("x", "y", "z", "r")
 
@@ -91,7 +104,7 @@ class Vec3:
         if isinstance(o, Vec3):
             raise TypeError("parameter must be float")   # fast_4d_matrix.c:220
         o = float(o)
-        return Vec3(self.x / o, self.y / o, self.z / o)
+        return Vec3(fdiv(self.x, o), fdiv(self.y, o), fdiv(self.z, o))
 
     def __neg__(self):
         return Vec3(-self.x, -self.y, -self.z)

@@ -473,7 +473,18 @@ static void push(Stack* st, Item it) {
   st->a[st->n++] = it;
 }
 
-typedef struct { const Scene* s; uint64_t seed; int x, y, sample; Stack st; Lit* lit; int gt1; } Tr;
+typedef struct {
+  const Scene* s; uint64_t seed; int x, y, sample; Stack st; Lit* lit; int gt1;
+  /* tree statistics (rto_tree_stats): the stack's entries that pass rt_map's cutoff, their peak, and,
+   * when lvl is set, the rays per tree level (level = trace_depth - the item's remaining depth) */
+  int live, max_live, nlvl; uint64_t* lvl;
+} Tr;
+
+static int item_live(const Item* it) { return !(it->depth <= 0 || vr(it->att) < 0.0001); }   /* ray_tracer.rb:52 */
+static void push_item(Tr* tr, Item it) {
+  tr->live += item_live(&it);
+  push(&tr->st, it);
+}
 
 /* ray_tracer.rb:292-298.  The running sum is the FIFO drain's (leaves in
  * emission order), but the drain runs after the whole tree (:39-45): a
@@ -489,6 +500,7 @@ static void rt_map(Tr* tr, Item it, V* sum, T* t) {                /* ray_tracer
   const Scene* s = tr->s;
   if (it.depth <= 0 || vr(it.att) < 0.0001) return;
   t->cnt[RTX_CNT_RAYS]++;
+  if (tr->lvl && s->cam.trace_depth - it.depth < tr->nlvl) tr->lvl[s->cam.trace_depth - it.depth]++;
   /* World#high_lights world.rb:83-98 */
   int nfired = 0;
   for (int l = 0; l < s->nlight; l++) {
@@ -537,10 +549,10 @@ static void rt_map(Tr* tr, Item it, V* sum, T* t) {                /* ray_tracer
   }
   uint64_t R = (uint64_t)pt + 3;
   Item c1 = {refl, it.depth - 1, vmul(it.att, o->refl_att), it.path * R + 1};
-  push(&tr->st, c1);
+  push_item(tr, c1);
   if (has_refr) {
     Item c2 = {refr, it.depth - 1, vmul(it.att, o->refr_att), it.path * R + 2};
-    push(&tr->st, c2);
+    push_item(tr, c2);
   }
   /* World#local_lights world.rb:72-80 at intersection + delta */
   V target = vadd(h.hit, h.delta);
@@ -564,7 +576,7 @@ static void rt_map(Tr* tr, Item it, V* sum, T* t) {                /* ray_tracer
       double phi = rto_rand(tr->seed, tr->x, tr->y, tr->sample, it.path, 2 * k + 1) * M_PI * 2;
       V dir = vadd(vsc(front, sin(theta)), vsc(vadd(vsc(left, cos(phi)), vsc(up, sin(phi))), cos(theta)));
       Item ci = {{target, dir}, it.depth - 1, vmul(it.att, att), it.path * R + 3 + (uint64_t)k};
-      push(&tr->st, ci);
+      push_item(tr, ci);
     }
   } else {
     int has_filter = 0;
@@ -596,11 +608,14 @@ static V trace_sync(Tr* tr, Ray ray, T* t) {                      /* ray_tracer.
   V sum = vmk(0.0, 0.0, 0.0);
   tr->st.n = 0;
   Item root = {ray, tr->s->cam.trace_depth, vmk(1.0, 1.0, 1.0), 1};
-  push(&tr->st, root);
+  tr->live = 0;
+  push_item(tr, root);
   tr->gt1 = 0;
   while (tr->st.n > 0) {
     Item it = tr->st.a[--tr->st.n];
+    tr->live -= item_live(&it);
     rt_map(tr, it, &sum, t);
+    if (tr->live > tr->max_live) tr->max_live = tr->live;
   }
   if (tr->gt1) raise_(t, RTX_ECOLOR_GT1, "color greater than 1");   /* the drain, after the tree */
   return sum;
@@ -712,6 +727,31 @@ int rto_render_pixels(Scene* s, int n, const int32_t* xy, uint64_t seed, double*
       snprintf(s->errmsg, sizeof s->errmsg, "pixel (%d,%d): %s", xy[2 * i], xy[2 * i + 1], t.msg);
     }
     if (counts) for (int k = 0; k < RTX_NCOUNT; k++) counts[k] += t.cnt[k];
+  }
+  tr_free(&tr);
+  return first;
+}
+
+/* Tree statistics of the pixels xy[2i], xy[2i+1], rendered as rto_render_pixels renders them.
+ * max_pending[i]: over the pixel's samples, the peak number of stacked siblings of a walk that
+ * stacks only the children that pass rt_map's cutoff (ray_tracer.rb:52) and holds the most recent
+ * of them instead of stacking it: the peak of (cutoff-passing entries of trace_sync's Array after
+ * an rt_map call) - 1.  levels[d] += the rays (RTX_CNT_RAYS events) of tree level d < nlev.
+ * status[i]: the pixel's rtx_status.  Returns the first error status. */
+int rto_tree_stats(Scene* s, int n, const int32_t* xy, uint64_t seed, int32_t* max_pending, uint64_t* levels,
+                   int nlev, int32_t* status) {
+  Tr tr;
+  tr_init(&tr, s, seed);
+  tr.lvl = levels;
+  tr.nlvl = nlev;
+  int first = 0;
+  for (int i = 0; i < n; i++) {
+    T t; memset(&t, 0, sizeof t);
+    tr.max_live = 0;
+    (void)render_at(&tr, xy[2 * i], xy[2 * i + 1], &t);
+    if (max_pending) max_pending[i] = tr.max_live > 0 ? tr.max_live - 1 : 0;
+    if (status) status[i] = t.err;
+    if (t.err && !first) first = t.err;
   }
   tr_free(&tr);
   return first;

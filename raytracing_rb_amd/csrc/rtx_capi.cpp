@@ -299,7 +299,8 @@ rtx_status rtx_set_option(rtx_context* c, const char* key, int64_t value) {
     c->opt_engine = value;
     return RTX_OK;
   }
-  if (!strcmp(key, "force_stack")) {
+  if (!strcmp(key, "force_stack")) {       // lanes engine: ray-stack entries per lane, rounded up to 8, 16, 32 or 64; 0 auto
+    if (value < 0 || value > 64) return fail(c, RTX_EINVAL, "force_stack must be in [0, 64]");
     c->opt_force_stack = value;
     return RTX_OK;
   }
@@ -491,7 +492,8 @@ rtx_status rtx_camera_set(rtx_context* c, const rtx_camera_desc* d) {
       return fail(c, RTX_EINVAL, "%dx%d pixels x %zu samples exceed 2^31 work items", d->width, d->height, ms);
   }
   if (d->trace_depth < 0 || d->trace_depth > 1000) return fail(c, RTX_EINVAL, "bad trace_depth");
-  if (d->monte_carlo_diffusion_times < 1) return fail(c, RTX_EINVAL, "monte_carlo_diffusion_times must be >= 1");
+  // 0: no path-tracing child at an unlit hit; diffuse_rate / 0.0 (world_object.rb:78) is computed and unused
+  if (d->monte_carlo_diffusion_times < 0) return fail(c, RTX_EINVAL, "monte_carlo_diffusion_times must be >= 0");
   uint32_t err = 0;
   CameraDev& k = c->cam;
   memset(&k, 0, sizeof k);
@@ -522,11 +524,23 @@ rtx_status rtx_camera_set(rtx_context* c, const rtx_camera_desc* d) {
 }
 
 // ------------------------------------------------------------------ render
-static int required_stack(const rtx_context* c) {
+// The lanes engine's ray-stack entries per lane for this camera (8, 16, 32 or 64) into maxs.  A camera
+// that needs more than 64, or more than a forced bucket holds, is refused here: a lane never finds its
+// stack full (rtx_device.h emit).
+static rtx_status required_stack(rtx_context* c, int& maxs) {
   // LIFO depth-first walk: a node at depth d >= 2 pushes <= 2 + pt children.
-  const long need = 1 + (long)(c->cam.depth > 1 ? c->cam.depth - 1 : 0) * (1 + c->cam.pt);
-  if (c->opt_force_stack) return stack_bucket((int)c->opt_force_stack);
-  return need > 64 ? -1 : stack_bucket((int)need);
+  const long need = 1 + (long)(c->cam.depth > 1 ? c->cam.depth - 1 : 0) * (1 + (long)c->cam.pt);
+  if (need > 64)
+    return fail(c, RTX_EINVAL, "trace_depth x monte_carlo_diffusion_times too large: a ray stack of %ld entries, at most 64",
+                need);
+  maxs = stack_bucket((int)need);
+  if (c->opt_force_stack) {
+    maxs = stack_bucket((int)c->opt_force_stack);
+    if (maxs < need)
+      return fail(c, RTX_EINVAL, "force_stack %lld: this camera needs a ray stack of %ld entries",
+                  (long long)c->opt_force_stack, need);
+  }
+  return RTX_OK;
 }
 
 // Sphere walk of the next launch (SphMode); the launchers fall back to scalar
@@ -841,8 +855,8 @@ rtx_status rtx_render_device(rtx_context* c, int32_t x0, int32_t y0, int32_t x1,
     return fail(c, RTX_EINVAL, "region [%d,%d)x[%d,%d) outside the %dx%d image", x0, x1, y0, y1,
                 c->cam.width, c->cam.height);
   if (row_stride < (size_t)(x1 - x0) * 3) return fail(c, RTX_EINVAL, "row_stride too small");
-  const int maxs = required_stack(c);
-  if (maxs < 0) return fail(c, RTX_EINVAL, "trace_depth x monte_carlo_diffusion_times too large");
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
   hipSetDevice(c->device);
   p.x0 = x0;
@@ -896,8 +910,8 @@ rtx_status rtx_render_tile_list_device(rtx_context* c, const int32_t* tiles, int
     if (list[k] < 0) return fail(c, RTX_EINVAL, "tile %d: negative index %d", k, list[k]);
     if (list[k] > ntiles) list[k] = ntiles;
   }
-  const int maxs = required_stack(c);
-  if (maxs < 0) return fail(c, RTX_EINVAL, "trace_depth x monte_carlo_diffusion_times too large");
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
   hipSetDevice(c->device);
   if (c->rowtiles != list) {
@@ -939,8 +953,8 @@ rtx_status rtx_render_tiles_device(rtx_context* c, int32_t tile_rows, int32_t ra
   rtx_status s = prep(c, p, seed);
   if (s) return s;
   if (tile_rows <= 0 || nranks <= 0 || rank < 0 || rank >= nranks) return fail(c, RTX_EINVAL, "bad tiling");
-  const int maxs = required_stack(c);
-  if (maxs < 0) return fail(c, RTX_EINVAL, "trace_depth x monte_carlo_diffusion_times too large");
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
   hipSetDevice(c->device);
   p.x0 = 0;
@@ -1608,8 +1622,8 @@ rtx_status rtx_trace(rtx_context* c, int32_t n, const double* rays, const int32_
   KParams p;
   rtx_status s = prep(c, p, seed);
   if (s) return s;
-  const int maxs = required_stack(c);
-  if (maxs < 0) return fail(c, RTX_EINVAL, "trace_depth x monte_carlo_diffusion_times too large");
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
   rtx_sync(c, nullptr);
   hipSetDevice(c->device);
@@ -1662,8 +1676,8 @@ rtx_status rtx_count_work(rtx_context* c, uint64_t seed, uint64_t counts[RTX_NCO
   KParams p;
   rtx_status s = prep(c, p, seed);
   if (s) return s;
-  const int maxs = required_stack(c);
-  if (maxs < 0) return fail(c, RTX_EINVAL, "trace_depth x monte_carlo_diffusion_times too large");
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
   hipSetDevice(c->device);
   const int W = c->cam.width, H = c->cam.height;

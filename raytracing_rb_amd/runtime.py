@@ -302,7 +302,10 @@ class Renderer:
     def engine(self):
         """Name of the ray-tree engine the next render of this scene and camera
         runs (read-only option "engine_effective": "engine", except that the
-        bounce-level engine hands cameras it cannot take to the lanes engine)."""
+        bounce-level engine hands monte_carlo_diffusion_times > 14 to the lanes
+        engine).  A camera whose ray stack, 1 +
+        (trace_depth - 1) * (1 + monte_carlo_diffusion_times), exceeds 64 entries
+        (every trace_depth > 64) is refused by both: RtxError, kind "invalid"."""
         return self.ENGINES[self.get_option("engine_effective")]
 
     def level_stats(self):

@@ -81,6 +81,31 @@ def tree_sums(levels):
     return sums, gt1
 
 
+def max_pending(levels):
+    """-> (peak [roots], live [levels]).  peak: per root, the most siblings stacked at once by a walk of
+    its tree in trace_sync's order that keeps the engines' discipline (rtx_device.h emit): only the
+    children that pass rt_map's cutoff (live_mask) exist for it, and of a node's live children the last
+    one, the one Array#pop returns next, is held, not stacked.  A camera of trace_depth D and pt
+    path-tracing children can reach (D - 1) * (1 + pt), one less than the `need` the lanes engine sizes
+    its stack by.  live: the live items per level, the rays rtx_level_stats counts."""
+    first = [np.cumsum(out["n_children"], dtype=np.int64) - out["n_children"] for _, out in levels]
+    live = [live_mask(level) for level, _ in levels]
+    nroot = len(levels[0][0]["rays"]) if levels else 0
+    peak = np.zeros(nroot, np.int64)
+    for r in range(nroot):
+        stack, held = [], (0, r) if live[0][r] else None
+        while held is not None or stack:
+            l, i = held if held is not None else stack.pop()
+            held = None
+            f, n = int(first[l][i]), int(levels[l][1]["n_children"][i])
+            kids = [(l + 1, f + j) for j in range(n) if live[l + 1][f + j]] if n else []
+            if kids:
+                stack.extend(kids[:-1])
+                held = kids[-1]
+            peak[r] = max(peak[r], len(stack))
+    return peak, np.array([int(m.sum()) for m in live], np.int64)
+
+
 # ------------------------------------------------------------------ the oracle as the callback
 def oracle_item(level, i):
     """Item i of a level as rt_ref.RayTracer.rt_map takes it, and its (x, y, sample)."""

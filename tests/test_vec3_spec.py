@@ -116,6 +116,23 @@ def test_div_by_vector_raises():
         Vec3.from_a(1.0, 1.0, 1.0) / Vec3.from_a(1.0, 1.0, 1.0)
 
 
+def test_div_by_zero_is_ieee(V):
+    """Vec3#/ is a plain C division (fast_4d_matrix.c:209-224): a zero divisor raises nothing.  It is
+    what diffuse_rate / pt_times.to_f is with monte_carlo_diffusion_times 0 (world_object.rb:78)."""
+    import math
+    inf = math.inf
+    for zero, s in ((0.0, 1.0), (-0.0, -1.0)):
+        q = V.from_a(0.5, -2.0, 0.0) / zero
+        a = q.to_a()
+        assert a[0] == s * inf and a[1] == -s * inf and math.isnan(a[2])
+        assert math.isnan(q.r)                          # sqrt(inf + inf + nan)
+        assert math.isnan((V.from_a(math.nan, 1.0, 1.0) / zero).to_a()[0])
+    assert (V.from_a(inf, -inf, 1.0) / 0.0).to_a() == [inf, -inf, inf]
+    assert (V.from_a(1.0, -1.0, 0.0) / inf).to_a() == [0.0, -0.0, 0.0]
+    assert math.copysign(1.0, (V.from_a(1.0, -1.0, 0.0) / inf).to_a()[1]) == -1.0
+    assert (V.from_a(1e308, -1e308, 1.0) / 1e-10).to_a() == [inf, -inf, 1e10]          # overflow, no raise
+
+
 def test_both_implementations_agree_bitwise():
     import random
     _abi.load_library()
