@@ -397,6 +397,36 @@ rtx_status rtx_render_at(rtx_context* ctx, int32_t x, int32_t y, uint64_t seed, 
 rtx_status rtx_trace(rtx_context* ctx, int32_t n, const double* rays, const int32_t* keys,
                      uint64_t seed, double* out_rgb);
 
+/* RayTracer#trace_sync for n explicit rays in device buffers, asynchronous on
+ * hip_stream, with a status per ray.  Needs the scene and a
+ * camera (trace_depth, monte_carlo_diffusion_times), as rtx_trace.
+ *   d_rays:   double[n][6] front, position, as rtx_trace; required.
+ *   d_keys:   int32[n][3] = x, y, sample: the RNG key of the ray's tree; any int32 values; required.
+ *   d_rgb:    double[n][3]; required; 8-byte alignment is enough.
+ *   d_status: int32[n] or NULL: the rtx_status of the ray tree's first raise in trace_sync's
+ *             order (rt_map's raises as the tree is walked, else rt_reduce's "color greater
+ *             than 1"), RTX_OK if none.
+ * A raising ray's colour is three quiet NaNs; other rays are unaffected.  Like the query
+ * calls it records nothing in rtx_sync's state and returns RTX_OK whatever the statuses hold.
+ * n == 0 is RTX_OK; RTX_EINVAL for n < 0, a NULL required pointer, no scene or camera, or a
+ * camera whose ray stack exceeds 64 entries (as rtx_trace).
+ * Engine: option "trace_engine" (below).  Through the bounce levels the rays are level 0 of
+ * the engine in batches of "lv_batch" rays; the staged ray records are always 96 bytes (the
+ * 80-byte record decodes the RNG key from a camera item), whatever "lv_ray_bytes" says; a ray
+ * that finds no room in the level buffers, or whose key has a negative x (the records' mark
+ * for "key not carried"), is traced whole by the lanes engine: the same bits either way.
+ * Split phases ("lv_split" 1) are not built for explicit rays: RTX_EINVAL under
+ * "trace_engine" 1, the lanes engine under -1.  rtx_level_stats, "lv_plan_last",
+ * "lv_sort_last" and rtx_kernel_time ("kernel_events") describe the call afterwards, with
+ * "camera samples" read as "rays".
+ * The call shares the context's level statistics, event pairs, lanes-engine ray stacks and
+ * work-counter ring with renders: as for rtx_render_device, calls on one context are issued
+ * from one thread at a time, and a call on another stream may not overlap a render or trace
+ * still running on this context unless the caller orders them (events or a sync); calls on
+ * one stream are ordered by the stream. */
+rtx_status rtx_trace_device(rtx_context* ctx, int32_t n, uint64_t seed, const double* d_rays,
+                            const int32_t* d_keys, double* d_rgb, int32_t* d_status, void* hip_stream);
+
 /* RayTracer#path_trace_sync(x, y, ray) for n rays (host buffers, rays as in
  * rtx_trace).  Never called by the reference, reproduced with its behaviour:
  * black below trace_depth 1 or on a miss, the highlight sum when a light's
@@ -527,7 +557,15 @@ rtx_status rtx_get_option(rtx_context* ctx, const char* key, int64_t* value);
          render, recorded by the launcher: bits 0-3 the sphere mode [SphMode, rtx_plan.h], 4-7 the hit ring's
          fields [0 none, 5 compact, 11 full], 8 the light buffer in LDS, 9 the raise gates in LDS, 10-11 the raise
          check [0 none, 1 through the buffers, 2 the widened walk], 12 the workgroup's claim counter placed, 16
-         and up the launch's dynamic LDS bytes; -1: no fused launch ran, e.g. lv_split). */
+         and up the launch's dynamic LDS bytes; -1: no fused launch ran, e.g. lv_split),
+         "trace_engine" (explicit rays, rtx_trace and rtx_trace_device: -1 [default] = rtx_trace runs the lanes
+         engine with its one raise per call, as ever, and rtx_trace_device runs the bounce levels from
+         RTX_TRACE_LEVELS_MIN_RAYS = 64 rays per call [rtx_capi.cpp; the smallest batch measured, DESIGN.md 3.22
+         has the table] and the lanes engine below; 0 = the lanes engine for both; 1 = the bounce levels for both: the
+         host rtx_trace then uploads, calls rtx_trace_device with a status buffer, downloads, fills raising
+         rays with NaN and returns the first raising ray's status by index, "... at ray i" in rtx_last_error;
+         1 falls back to the lanes engine where "engine_effective" would, monte_carlo_diffusion_times > 14;
+         same bits), read-only "trace_engine_last" (the engine the last trace call ran, 0 or 1). */
 
 /* ---- Vec3 (fast_4d_matrix.c), pure host functions ------------------------ */
 rtx_vec3   rtx_vec3_from_a(double x, double y, double z);                   /* :75-84   */

@@ -115,10 +115,12 @@ class RayTracer:
             raise ValueError("rt_map needs keys: (x, y, sample, remaining trace_depth) per ray")
         return self._r.rt_map(rays, keys, att=att, paths=paths, seed=self.seed)
 
-    def trace_many(self, fronts, positions, keys):
-        """Batched trace_sync: fronts/positions [n, 3], keys [n, 3] = (x, y, sample)."""
+    def trace_many(self, fronts, positions, keys, check=True):
+        """Batched trace_sync: fronts/positions [n, 3], keys [n, 3] = (x, y, sample).
+        check=False: (colours, per-ray rtx_status) instead of RtxError for the
+        first raising ray (Renderer.trace)."""
         rays = np.concatenate([np.asarray(fronts, np.float64), np.asarray(positions, np.float64)], axis=1)
-        return self._r.trace(rays, keys, seed=self.seed)
+        return self._r.trace(rays, keys, seed=self.seed, check=check)
 
 
 class Camera:

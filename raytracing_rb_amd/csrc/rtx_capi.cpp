@@ -96,6 +96,8 @@ struct rtx_context {
   int64_t opt_lv_sort_bits = 0;      // bounce levels: 2^bits origin cells per axis (3 or 4); 0 auto: 4 above 512 spheres, else 3
   int64_t opt_lv_sort_copy = 0;      // bounce levels: 1 = binning copies the rays' records into bin order (r11i: C4 296 -> 342 ms, off)
   int64_t opt_lbuf = PlanOpts{}.lbuf;              // bounce levels: 1 = shadow walks through the light buffer where it is staged (§3.18)
+  int64_t opt_trace_engine = -1;     // explicit rays: 0 lanes, 1 bounce levels, -1 rtx_trace lanes / rtx_trace_device by batch size
+  int64_t last_trace_engine = 0;     // the engine the last trace call ran (read-only option trace_engine_last)
   int n_cus = 0;                     // compute units of the device (hipDeviceAttributeMultiprocessorCount)
   unsigned long long* d_lvstats = nullptr;   // rtx_level_stats of the last bounce-level render call
   int64_t last_sort_levels = 0;              // levels per batch the last bounce-level render binned (lv_sort_last)
@@ -254,6 +256,10 @@ rtx_status rtx_get_option(rtx_context* c, const char* key, int64_t* value) {
     *value = c->last_plan;                    // fused level launch, as the launcher recorded it (-1: none ran)
     return RTX_OK;
   }
+  if (!strcmp(key, "trace_engine_last")) {    // read-only: the engine the last rtx_trace / rtx_trace_device call ran
+    *value = c->last_trace_engine;
+    return RTX_OK;
+  }
   if (!strcmp(key, "lv_sort_effective")) {    // read-only: whether the next whole-frame bounce-level render bins its levels
     *value = c->have_cam && lv_sort_from(c, lv_frame_items(c)) > 0 ? 1 : 0;
     return RTX_OK;
@@ -283,7 +289,7 @@ rtx_status rtx_get_option(rtx_context* c, const char* key, int64_t* value) {
       {"lv_fin_grid", c->opt_lv_fin_grid}, {"lv_ray_bytes", c->opt_lv_ray_bytes},
       {"exact_raises", c->opt_exact_raises}, {"lv_hl_cap", c->opt_lv_hl_cap}, {"lv_sort", c->opt_lv_sort},
       {"lv_sort_from", c->opt_lv_sort_from}, {"lv_sort_bits", c->opt_lv_sort_bits}, {"lbuf", c->opt_lbuf},
-      {"lv_sort_copy", c->opt_lv_sort_copy}};
+      {"lv_sort_copy", c->opt_lv_sort_copy}, {"trace_engine", c->opt_trace_engine}};
   for (const auto& t : tab)
     if (!strcmp(key, t.k)) {
       *value = t.v;
@@ -406,6 +412,11 @@ rtx_status rtx_set_option(rtx_context* c, const char* key, int64_t value) {
   if (!strcmp(key, "lbuf")) {              // bounce levels: shadow walks through the light buffer (same bits)
     if (value != 0 && value != 1) return fail(c, RTX_EINVAL, "lbuf must be 0 or 1");
     c->opt_lbuf = value;
+    return RTX_OK;
+  }
+  if (!strcmp(key, "trace_engine")) {      // explicit rays: 0 lanes, 1 bounce levels, -1 auto (rtx_trace_device by batch size)
+    if (value < -1 || value > 1) return fail(c, RTX_EINVAL, "trace_engine must be -1, 0 or 1");
+    c->opt_trace_engine = value;
     return RTX_OK;
   }
   if (!strcmp(key, "lv_ray_bytes")) {      // bounce levels: staged ray record size (0 auto)
@@ -645,9 +656,11 @@ static int lv_sort_bits(const rtx_context* c) {
   return c->opt_lv_sort_bits ? (int)c->opt_lv_sort_bits : c->scene.n_sphere > 512 ? 4 : 3;
 }
 
-static bool levels_engine(const rtx_context* c) {
-  return c->opt_engine == 1 && c->cam.depth <= LV_MAXL && c->cam.pt + 2 <= 16 && c->scene.n_light <= 255;
+// the bounce-level engine's limits: its levels, a ray's child slots, a record's leaves
+static bool levels_fit(const rtx_context* c) {
+  return c->cam.depth <= LV_MAXL && c->cam.pt + 2 <= 16 && c->scene.n_light <= 255;
 }
+static bool levels_engine(const rtx_context* c) { return c->opt_engine == 1 && levels_fit(c); }
 
 // render_region for the bounce-level engine: batches of
 // 8x8 tiles, one launch per tree level, the trees reduced by k_tree_finalize.
@@ -1615,16 +1628,180 @@ rtx_status rtx_render_at(rtx_context* c, int32_t x, int32_t y, uint64_t seed, do
   return rtx_render(c, x, y, x + 1, y + 1, seed, rgb, 3);
 }
 
-rtx_status rtx_trace(rtx_context* c, int32_t n, const double* rays, const int32_t* keys, uint64_t seed,
-                     double* out) {
-  if (!c || n < 0 || (n && (!rays || !keys || !out))) return fail(c, RTX_EINVAL, "bad arguments");
+// ------------------------------------------------------------------ explicit rays
+// rtx_trace_device with "trace_engine" -1 runs the bounce levels from this many
+// rays and the lanes engine below (the smallest measured batch
+// of C2 lens rays, 2^6 .. 2^20 in powers of four, at which the levels' median
+// was at or below the lanes': the smallest one measured, 0.130 against 0.162 ms).
+#ifndef RTX_TRACE_LEVELS_MIN_RAYS
+#define RTX_TRACE_LEVELS_MIN_RAYS 64
+#endif
+
+// One trace call on `stream`: the batch buffers (stream-ordered from the
+// device pool, as render_levels'; one part), then launch_trace_levels.  Buffer
+// sizing is render_levels' with "camera samples" read as "rays"; the staged
+// records are always 96 B (the 80-B record decodes the RNG key from a camera
+// item, which an explicit ray is not), whatever "lv_ray_bytes" says.
+static rtx_status trace_levels(rtx_context* c, KParams& p, int maxs, bool levels, int32_t* d_status,
+                               hipStream_t stream) {
+  const size_t n0 = (size_t)std::max<int64_t>(1, std::min<int64_t>(c->opt_lv_batch, p.nrays));
+  const size_t fl = (size_t)c->opt_lv_floor;
+  const size_t want = std::max<size_t>(std::max<size_t>(64, fl), n0 * (size_t)c->opt_lv_stage_pct / 100);
+  const size_t lcap = std::max<size_t>(std::max(n0, 4 * fl), n0 * (size_t)c->opt_lv_rec_pct / 100);
+  int slog2 = 0;
+  while (((size_t)LV_SLICES << slog2) < want) slog2++;
+  const size_t scap = (size_t)LV_SLICES << slog2;
+  if (levels && (scap > UINT32_MAX / 2 || lcap > UINT32_MAX / 2))
+    return fail(c, RTX_EINVAL, "bounce-level buffers exceed 2^31 records: lower lv_batch");
+  const int rec_bytes = levels_rec_bytes(c->scene.n_light);
+  const size_t hlcap = c->opt_lv_hl_cap > 0 ? (size_t)c->opt_lv_hl_cap : std::max<size_t>(4096, lcap / 256);
+  const int sort_from = levels ? lv_sort_from(c, n0) : 0;
+  const bool sort = sort_from > 0, sort_copy = sort && c->opt_lv_sort_copy == 1;
+  const size_t sz_ctl = al256(sizeof(LevelCtl)), sz_redo = al256(n0 * 4), sz_smp = al256(n0 * 32),
+               sz_stage = levels ? al256(scap * RAY_BYTES) : 0, sz_rec = levels ? al256(lcap * (size_t)rec_bytes) : 0,
+               sz_hlq = levels ? al256(hlcap * 64) : 0, sz_key = sort ? al256(scap * 2) : 0,
+               sz_perm = sort ? al256(scap * 8) : 0, sz_bins = sort ? al256((size_t)LV_BINS * 8) : 0,
+               sz_sorted = sort_copy ? sz_stage : 0;
+  const size_t total = sz_ctl + 2 * sz_redo + sz_smp + 2 * sz_stage + sz_rec + sz_hlq + sz_key + sz_perm + sz_bins +
+                       sz_sorted + 256;
+  if (!c->d_lvstats) HIPCHK(c, hipMalloc(&c->d_lvstats, sizeof(unsigned long long) * (LV_MAXL + 3)));
+  char* buf = nullptr;
+  HIPCHK(c, hipMallocAsync((void**)&buf, total, stream));
+  char* q = buf;
+  p.lv_ctl = (LevelCtl*)q;                  q += sz_ctl;
+  p.lv_redo_of = (int32_t*)q;               q += sz_redo;
+  p.lv_redo_list = (int32_t*)q;             q += sz_redo;
+  p.lv_redo_smp = (double*)q;               q += sz_smp;
+  p.lv_stage[0] = (double*)q;               q += sz_stage;
+  p.lv_stage[1] = (double*)q;               q += sz_stage;
+  p.lv_rec = q;                             q += sz_rec;
+  p.lv_hlq = levels ? (double*)q : nullptr; q += sz_hlq;
+  p.lv_hlq_cap = levels ? (uint32_t)hlcap : 0;
+  p.lv_key = sort ? (uint16_t*)q : nullptr;       q += sz_key;
+  p.lv_perm = sort ? (uint2*)q : nullptr;         q += sz_perm;
+  p.lv_bins = sort ? (uint32_t*)q : nullptr;      q += sz_bins;
+  p.lv_sorted = sort_copy ? (double*)q : nullptr; q += sz_sorted;
+  p.extra_count = (int32_t*)q;                 // (k_level_begin zeroes it)
+  p.lv_sort = sort_from;
+  p.lv_cell_bits = lv_sort_bits(c);
+  p.lv_lbuf = (int32_t)c->opt_lbuf;
+  p.lv_split = 0;
+  p.lv_compact = (int32_t)c->opt_lv_compact;
+  p.lv_grid_div = (int32_t)c->opt_lv_grid_div;
+  // the levels' overflow re-trace keeps the render's grid cap; the lanes engine takes every resident workgroup
+  p.lv_redo_blocks = levels ? (int32_t)c->opt_lv_redo_blocks : 0;
+  p.lv_static_pct = c->opt_lv_static >= 0 ? (int32_t)c->opt_lv_static : (c->scene.n_sphere <= 512 ? 100 : 50);
+  p.lv_round = c->opt_lv_round >= 0 ? (int32_t)c->opt_lv_round : (c->scene.n_sphere <= 512 ? 8 : 32);
+  p.lds_sched = -1;
+  p.lv_scap = (uint32_t)scap;
+  p.lv_slice_log2 = slog2;
+  p.lv_hslice_log2 = 0;
+  p.lv_lcap = (uint32_t)lcap;
+  p.lv_rec_bytes = rec_bytes;
+  p.lv_ray_dbl = 12;
+  p.lv_last_level = c->cam.depth >= 1 ? c->cam.depth - 1 : -1;
+  p.lv_acc = c->d_lvstats;
+  p.samples = nullptr;
+  c->last_sort_levels = sort ? std::max(0, c->cam.depth - sort_from) : 0;
+  c->last_plan = -1;
+  KernelEvents kev{c->ev, 0, rtx_context::MAX_EV};
+  if (c->opt_kernel_events && !c->ev[0])
+    for (int k = 0; k < 2 * rtx_context::MAX_EV; k++) HIPCHK(c, hipEventCreate(&c->ev[k]));
+  const int mode = c->opt_sphere_src == -1 ? levels_auto_mode(c->scene, sph_mode(c), (int)c->opt_lv_compact, 0)
+                                           : sph_mode(c);
+  const hipError_t e = launch_trace_levels(p, levels ? mode : sph_mode(c), maxs, std::max(1, c->cam.depth), (int)n0,
+                                           levels, d_status, stream, c->opt_kernel_events ? &kev : nullptr,
+                                           &c->last_plan);
+  if (c->opt_kernel_events) c->n_ev = kev.n;
+  const hipError_t f = hipFreeAsync(buf, stream);
+  HIPCHK(c, e);
+  HIPCHK(c, f);
+  return RTX_OK;
+}
+
+rtx_status rtx_trace_device(rtx_context* c, int32_t n, uint64_t seed, const double* d_rays, const int32_t* d_keys,
+                            double* d_rgb, int32_t* d_status, void* stream) {
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative ray count");
   if (n == 0) return RTX_OK;
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  if (!d_rays) return fail(c, RTX_EINVAL, "null rays");
+  if (!d_keys) return fail(c, RTX_EINVAL, "null keys");
+  if (!d_rgb) return fail(c, RTX_EINVAL, "null rgb buffer");
   KParams p;
   rtx_status s = prep(c, p, seed);
   if (s) return s;
   int maxs = 0;
   if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
+  const bool want = c->opt_trace_engine == 1 || (c->opt_trace_engine == -1 && (int64_t)n >= RTX_TRACE_LEVELS_MIN_RAYS);
+  bool levels = want && levels_fit(c);
+  if (levels && c->opt_lv_split != 0 && c->scene.n_light <= LV_SPLIT_MAX_LIGHTS) {
+    if (c->opt_trace_engine == 1)
+      return fail(c, RTX_EINVAL, "lv_split 1: explicit rays run the fused level launches only");
+    levels = false;
+  }
+  p.rays = d_rays;
+  p.keys = d_keys;
+  p.nrays = n;
+  p.out = d_rgb;
+  if ((s = trace_levels(c, p, maxs, levels, d_status, (hipStream_t)stream))) return s;
+  c->last_trace_engine = levels ? 1 : 0;
+  if (!levels) {                               // (rtx_level_stats, lv_plan_last: no level render)
+    c->last_sort_levels = 0;
+    c->last_plan = -1;
+  }
+  return RTX_OK;
+}
+
+// rtx_trace under "trace_engine" 1: upload, rtx_trace_device with a status
+// buffer, download; the first raising ray by index is the call's status.
+static rtx_status trace_host_levels(rtx_context* c, int32_t n, const double* rays, const int32_t* keys, uint64_t seed,
+                                    double* out) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  // as the lanes path: wait for the context's earlier work (it may still read the scratch buffer
+  // that is reused and perhaps reallocated below) and discard the raises nobody collected
+  rtx_sync(c, nullptr);
+  const size_t rb = sizeof(double) * 6 * n, kb = sizeof(int32_t) * 3 * n, ob = sizeof(double) * 3 * n,
+               sb = sizeof(int32_t) * (size_t)n;
+  rtx_status s = ensure_scratch(c, rb + ob + kb + sb + 64);
+  if (s) return s;
+  char* base = (char*)c->d_scratch;
+  double* d_rays = (double*)base;
+  double* d_out = (double*)(base + rb);
+  int32_t* d_keys = (int32_t*)(base + rb + ob);
+  int32_t* d_status = (int32_t*)(base + rb + ob + kb);
+  HIPCHK(c, hipMemcpy(d_rays, rays, rb, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(d_keys, keys, kb, hipMemcpyHostToDevice));
+  if ((s = rtx_trace_device(c, n, seed, d_rays, d_keys, d_out, d_status, nullptr))) return s;
+  std::vector<int32_t> st((size_t)n);
+  HIPCHK(c, hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(st.data(), d_status, sb, hipMemcpyDeviceToHost));
+  int32_t first = -1, kinds = 0;
+  for (int32_t i = 0; i < n; i++)
+    if (st[i]) {
+      if (first < 0) first = i;
+      kinds |= 1 << st[i];
+    }
+  if (first < 0) return RTX_OK;
+  const rtx_status r = (rtx_status)st[first];
+  return fail(c, r, "%s at ray %llu%s", rtx_status_string(r), (unsigned long long)first,
+              __builtin_popcount(kinds) > 1 ? " (and other errors)" : "");
+}
+
+rtx_status rtx_trace(rtx_context* c, int32_t n, const double* rays, const int32_t* keys, uint64_t seed,
+                     double* out) {
+  if (!c || n < 0 || (n && (!rays || !keys || !out))) return fail(c, RTX_EINVAL, "bad arguments");
+  if (n == 0) return RTX_OK;
+  if (c->opt_trace_engine == 1) return trace_host_levels(c, n, rays, keys, seed, out);
+  KParams p;
+  rtx_status s = prep(c, p, seed);
+  if (s) return s;
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
+  if ((s = ensure_stack(c, p, maxs))) return s;
+  c->last_trace_engine = 0;
   rtx_sync(c, nullptr);
   hipSetDevice(c->device);
   const size_t rb = sizeof(double) * 6 * n, kb = sizeof(int32_t) * 3 * n, ob = sizeof(double) * 3 * n;

@@ -43,7 +43,9 @@ namespace rtx {
 // the sample's colour and first raise go to p.samples, and k_finalize does the
 // mean / variance / extra-sample decision.  SRC_EXTRA: the extra samples of the
 // pixels k_finalize listed.  SRC_RAYS: one lane per explicit ray running
-// RayTracer#trace_sync (rtx_trace).  SPH: where the sphere walk reads its
+// RayTracer#trace_sync (rtx_trace).  SRC_RAYLIST: the explicit rays a trace
+// call's bounce-level batch listed (lv_redo_list; rtx_trace_device), result to
+// lv_redo_smp as SRC_LIST.  SPH: where the sphere walk reads its
 // records (SphMode, rtx_launch.h).  BS: threads per workgroup.
 template <bool COUNT, int WPS, int SPH, int SRC, int BS, bool PP>
 __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
@@ -53,7 +55,9 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
   static_assert(!COUNT || SPH == SPH_LIN_LDS || SPH == SPH_LIN_SCALAR, "counting launches walk linearly");
   const SceneDev& S = p.scene;                // kernel argument: scalar loads
   const CameraDev& cam = *p.cam;
-  if (SRC == SRC_LIST && p.lv_ctl->redo_n == 0) return;   // nothing to re-render (the usual case)
+  constexpr bool EXPL = SRC == SRC_RAYS || SRC == SRC_RAYLIST;   // the item is an explicit ray
+  constexpr bool LIST = SRC == SRC_LIST || SRC == SRC_RAYLIST;   // the items are the batch's re-render list
+  if (LIST && p.lv_ctl->redo_n == 0) return;   // nothing to re-render (the usual case)
   // Dynamic LDS: the sphere records of the walk (SPH_LIN_LDS: float32 pre-test
   // records; SPH_BVH_LDS: hierarchy nodes at 0, leaf records at lds_leaf),
   // then (BVH modes) the per-wave traversal stacks and per-lane cover lists.
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
   const int ms = p.max_samples > p.pre ? p.max_samples : p.pre;   // sample records per pixel
   const int nwork = SRC == SRC_PIXELS ? tiles_x * ((p.nrows + 7) >> 3) * 64 * pre
                     : SRC == SRC_EXTRA ? *p.extra_count * n_extra
-                    : SRC == SRC_LIST ? (int)p.lv_ctl->redo_n : nrays;
+                    : LIST ? (int)p.lv_ctl->redo_n : nrays;
   int x = 0, y = 0, row = 0, px_ = 0, item_ = 0;
   V3 tgt = v3(0.0, 0.0, 0.0);
 
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
               p.out[3 * row + 2] = sum.z;
               if (err) record_error(p.err, err, (unsigned long long)row);
             } else {                            // one camera sample: colour + first raise
-              double2* q = SRC == SRC_LIST
+              double2* q = LIST
                                ? reinterpret_cast<double2*>(p.lv_redo_smp + (size_t)item_ * 4)
                                : reinterpret_cast<double2*>(p.samples + ((size_t)row * p.nx + px_) * ms * 4 +
                                                             (size_t)sample * 4);
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
           }
           started = true;
           sum = v3(0.0, 0.0, 0.0);
-          if (SRC != SRC_RAYS) {
+          if (!EXPL) {
             cur.ray = lens_ray(cam, tgt, x, y, sample, p.seed);
             if (COUNT) cnt[C_PRIMARY]++;
           } else {
@@ -217,7 +221,7 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
         if (k >= nwork) {
           mode = M_DONE;
           if (RTX_STAMPS) w_dry = wall();
-        } else if (SRC != SRC_RAYS) {
+        } else if (!EXPL) {
           if (RTX_STAMPS) {
             const unsigned long long w = wall();
             if (w_item && w - w_item > w_maxitem) w_maxitem = w - w_item;
@@ -264,6 +268,10 @@ __global__ __launch_bounds__(BS, WPS) void k_render(KParams p) {
           }
         } else {
           row = k;
+          if (SRC == SRC_RAYLIST) {             // a trace call's listed ray, re-traced here
+            item_ = k;
+            row = p.lv_redo_list[k];
+          }
           x = keys[3 * row];
           y = keys[3 * row + 1];
           started = false;
@@ -748,7 +756,7 @@ static hipError_t launch_one(KParams p, int maxs, int nwork, hipStream_t s) {
   // lv_redo_blocks) so that it does not wait for a whole chip's worth of CUs
   // that another stream's level launch holds (the batch's tree reduction
   // waits behind it).
-  if (SRC == SRC_LIST && p.lv_redo_blocks > 0) blocks = std::min<long>(blocks, p.lv_redo_blocks);
+  if ((SRC == SRC_LIST || SRC == SRC_RAYLIST) && p.lv_redo_blocks > 0) blocks = std::min<long>(blocks, p.lv_redo_blocks);
   if (blocks <= 0) return hipSuccess;
   if (!g_work_zeroed) e = hipMemsetAsync(p.work, 0, sizeof(int), s);
   if (e != hipSuccess) return e;
@@ -835,6 +843,16 @@ hipError_t launch_redo(const KParams& q, int mode, int maxs, int n, hipStream_t 
   g_work_zeroed = true;
   if (mode == SPH_BVH_MIX || mode == SPH_BVH_LDSX || mode == SPH_BVH_QLDS) mode = resolve_mode(q.scene, SPH_BVH_LDS);   // (see launch_render)
   const hipError_t e = launch_src<SRC_LIST>(q, mode, false, maxs, n, s);
+  g_work_zeroed = false;
+  return e;
+}
+
+// The same for a trace call's batch: the listed explicit rays (SRC_RAYLIST).
+hipError_t launch_redo_rays(const KParams& q, int mode, int maxs, int n, hipStream_t s) {
+  if (maxs != 8 && maxs != 16 && maxs != 32 && maxs != 64) return hipErrorInvalidValue;
+  g_work_zeroed = true;
+  if (mode == SPH_BVH_MIX || mode == SPH_BVH_LDSX || mode == SPH_BVH_QLDS) mode = resolve_mode(q.scene, SPH_BVH_LDS);   // (see launch_render)
+  const hipError_t e = launch_mode<false, SRC_RAYLIST>(q, mode, maxs, n, s);
   g_work_zeroed = false;
   return e;
 }

@@ -185,6 +185,14 @@ hipError_t launch_path_trace(KParams p, hipStream_t s);
 // The lanes engine's re-render of the level-0 items listed in lv_redo_list
 // (SRC_LIST; exits at once when the list is empty).
 hipError_t launch_redo(const KParams& q, int mode, int maxs, int n, hipStream_t s);
+// The same for a trace call's batch: the explicit rays listed in lv_redo_list (SRC_RAYLIST).
+hipError_t launch_redo_rays(const KParams& q, int mode, int maxs, int n, hipStream_t s);
+// RayTracer#trace_sync for the p.nrays explicit rays p.rays / p.keys (device buffers) -> p.out [n][3] and
+// status int32[n] (or null), in batches of `batch` rays.  levels: through the bounce
+// levels (the lv_* buffers of `p` sized for `batch` level-0 items, 96-B staged records, no split phases);
+// else every ray through the lanes engine (lv_ctl and the lv_redo_* buffers only).  Nothing goes to p.err.
+hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batch, bool levels, int32_t* status,
+                               hipStream_t s, KernelEvents* kev = nullptr, int64_t* plan_out = nullptr);
 int read_level_stamps(unsigned long long* out, int reset);   // diagnostic builds
 hipError_t launch_quantize(const double* rgb, int w, int h, size_t stride, int blend, uint8_t* out,
                            hipStream_t s);

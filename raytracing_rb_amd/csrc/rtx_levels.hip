@@ -651,11 +651,42 @@ __device__ __forceinline__ bool lv_walk(const KParams& p, char* lds, bool ext, V
 // item, Camera#lens_func) or the staged child at slot `idx`.  `valid` false
 // for the padding of an 8x8 tile.  CHUNK: the wave's active lanes hold consecutive
 // items of one level-0 chunk (the first half of the level kernels), see decode_item.
-template <bool CHUNK = false>
+// SRC: what a level-0 item is.  LSRC_CAMERA: a camera sample (renders).
+// LSRC_RAYS: ray `idx` of an explicit batch (rtx_trace_device):
+// p.rays[idx] with the RNG key p.keys[idx]; items past p.nrays are padding.
+// Only the level-0 kernels of a trace call are instantiated for it
+// (k_level_rays, k_level_c_rays): every other kernel compiles from LSRC_CAMERA.
+enum { LSRC_CAMERA = 0, LSRC_RAYS = 1 };
+__device__ __forceinline__ void lv_ray_explicit(const KParams& p, uint32_t idx, Ray& r, int& x, int& y, int& sample) {
+  const double* q = p.rays + (size_t)idx * 6;
+  r.d = v3p(q);
+  r.o = v3p(q + 3);
+  const int32_t* k = p.keys + (size_t)idx * 3;
+  x = k[0];
+  y = k[1];
+  sample = k[2];
+}
+// The staged records mark "key not carried" by x < 0 (lv_ray_tail, lv_ray_key),
+// so an explicit ray whose key has a negative x cannot carry it to its
+// children: its tree goes to the lanes engine whole (lv_redo), exact either way.
+template <int SRC>
+__device__ __forceinline__ bool lv_key_unstageable(int x) { return SRC == LSRC_RAYS && x < 0; }
+
+template <bool CHUNK = false, int SRC = LSRC_CAMERA>
 __device__ __forceinline__ void lv_ray(const KParams& p, int level, uint32_t idx, Item& cur, int& root, int& x, int& y,
                                        int& sample, bool& valid) {
   valid = true;
   if (level == 0) {
+    if constexpr (SRC == LSRC_RAYS) {
+      root = (int)idx;
+      valid = idx < (uint32_t)p.nrays;
+      if (valid) {
+        lv_ray_explicit(p, idx, cur.ray, x, y, sample);
+        cur.att = v3(1.0, 1.0, 1.0);
+        cur.path = 1;
+      }
+      return;
+    }
     root = (int)idx;
     const ItemPos ip = decode_item<CHUNK>(p, root);
     x = p.x0 + ip.px;
@@ -708,7 +739,7 @@ struct LvFirst {
 // staged child lazily) and its own hit frame and shadow loop: built from these
 // functions it rendered the same bits, but C4 (k_level_c<SPH_BVH_QLDS>, at
 // 256 VGPRs) 0.8 % slower, 262.4 against 260.5 ms, 1.5 ms of it the first half.
-template <int SPH, int BS>
+template <int SPH, int BS, int SRC = LSRC_CAMERA>
 __device__ __forceinline__ void lv_first_half(const KParams& p, char* lds, int level, uint32_t slot, uint32_t i,
                                               uint32_t base, int depth, bool& active, LvFirst& f, LvStamps* st) {
   const SceneDev& S = p.scene;
@@ -716,8 +747,12 @@ __device__ __forceinline__ void lv_first_half(const KParams& p, char* lds, int l
   bool alive = false;
   if (active) {
     bool valid;
-    lv_ray<true>(p, level, slot, f.cur, f.root, f.x, f.y, f.sample, valid);   // (level 0: slot = i, dense)
+    lv_ray<true, SRC>(p, level, slot, f.cur, f.root, f.x, f.y, f.sample, valid);   // (level 0: slot = i, dense)
     if (level == 0) p.lv_redo_of[i] = -1;     // no overflow yet (lv_redo)
+    if (level == 0 && valid && lv_key_unstageable<SRC>(f.x)) {
+      lv_redo(p, f.root);
+      valid = false;
+    }
     active = valid;                           // tile padding: no record
     alive = valid && (level > 0 || !(depth <= 0 || vr(f.cur.att) < 0.0001));   // rt_map's cutoff (ray_tracer.rb:52)
     if (active && base + i >= p.lv_lcap) {    // no room for this ray's record
@@ -935,7 +970,7 @@ __device__ __forceinline__ void lv_finish(const KParams& p, int level, int slice
 
 // Level `level` (0 .. trace_depth-1) of one batch in one launch (option
 // lv_split = 0).  Persistent, static chunk schedule.
-template <int SPH, int BS, int XR>
+template <int SPH, int BS, int XR, int SRC = LSRC_CAMERA>
 __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
   const SceneDev& S = p.scene;
   extern __shared__ float4 lds_sph[];
@@ -960,7 +995,7 @@ __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
     uint32_t slot, i;
     bool active = lv_chunk_item(p, in, level, chunk, slot, i);   // i: the ray's dense index in the level
     LvFirst f;
-    lv_first_half<SPH, BS>(p, lds, level, slot, i, base, depth, active, f, &st);
+    lv_first_half<SPH, BS, SRC>(p, lds, level, slot, i, base, depth, active, f, &st);
     uint32_t errS = 0, errP = 0;
     LvFrame fr;
     lv_hit_frame(S, f.shade, f.besti, f.cur.ray, f.hit, f.hin, fr, errS);
@@ -981,6 +1016,14 @@ template <int SPH, int BS, int XR>
 __global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level(KParams p, int level) {
   k_level_body<SPH, BS, XR>(p, level);
   lv_level_done(p, level + 1);
+}
+
+// Level 0 of a trace call (rtx_trace_device): the batch's explicit rays.  The
+// level is a constant, so the staged-child arms of the body fold away.
+template <int SPH, int BS, int XR>
+__global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level_rays(KParams p, int) {
+  k_level_body<SPH, BS, XR, LSRC_RAYS>(p, 0);
+  lv_level_done(p, 1);
 }
 
 // ----------------------------------------------------------------- hit compaction
@@ -1009,7 +1052,7 @@ __global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level(KParams p, int level)
 // the queue; level 0: Camera#lens_func re-evaluated for the item's key).
 // (LV_RING, LV_RING_FIELDS, LV_RING_FIELDS_SMALL and the rings' bytes per wave: rtx_plan.h)
 
-template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
+template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT, int SRC = LSRC_CAMERA>
 __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
   static_assert(RF == LV_RING_FIELDS || RF == LV_RING_FIELDS_SMALL, "ring layout");
   constexpr int FI = RF == LV_RING_FIELDS ? 9 : 3;   // ring field of {dense index, queue slot}
@@ -1054,8 +1097,12 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
         if (active) {
           bool valid = true;
           if (level == 0) {
-            lv_ray<true>(p, level, slot, cur, root, x, y, sample, valid);   // (slot = i, dense)
+            lv_ray<true, SRC>(p, level, slot, cur, root, x, y, sample, valid);   // (slot = i, dense)
             p.lv_redo_of[i] = -1;
+            if (valid && lv_key_unstageable<SRC>(x)) {
+              lv_redo(p, root);
+              valid = false;
+            }
           } else {
             const double2 a = qs[0], b = qs[1], c = qs[2];
             cur.ray.o = v3(a.x, a.y, b.x);
@@ -1152,7 +1199,14 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
       hin = ((uint32_t)be >> 31) != 0;
       errA = (uint32_t)(be >> 32) & 0xffu;
       errL = (uint32_t)(be >> 40) & 0xffu;
-      if (level == 0) {                       // the camera sample: item i (lv_ray)
+      if (level == 0 && SRC == LSRC_RAYS) {   // the explicit ray i and its key again (lv_ray)
+        root = (int)i;
+        Ray again;
+        lv_ray_explicit(p, i, again, x, y, sample);
+        cur.att = v3(1.0, 1.0, 1.0);
+        cur.path = 1;
+        if (RF != LV_RING_FIELDS) cur.ray = again;
+      } else if (level == 0) {                // the camera sample: item i (lv_ray)
         root = (int)i;
         const ItemPos ip = decode_item(p, root);
         x = p.x0 + ip.px;
@@ -1230,6 +1284,13 @@ template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
 __global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level_c(KParams p, int level) {
   k_level_c_body<SPH, BS, RF, LAST, XR, SORT>(p, level);
   lv_level_done(p, level + 1);
+}
+
+// k_level_c for level 0 of a trace call (see k_level_rays).
+template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
+__global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level_c_rays(KParams p, int) {
+  k_level_c_body<SPH, BS, RF, LAST, XR, SORT, LSRC_RAYS>(p, 0);
+  lv_level_done(p, 1);
 }
 
 // ----------------------------------------------------------------- split phases
@@ -1638,6 +1699,47 @@ __global__ __launch_bounds__(256) void k_tree_finalize_extra(KParams p, int nlev
   if (err) record_error(p.err, err, px_key(x, y, cam.height, 1));
 }
 
+// A trace call's reduction (rtx_trace_device): one thread per
+// explicit ray of the batch sums its tree, or takes the lanes engine's record
+// of a listed ray (lv_sample), as k_tree_finalize does for a camera sample,
+// without render_at's pixel stage: the colour to p.out[3 i] (scalar stores:
+// the buffer may be only 8-byte aligned) and the rtx_status of the tree's
+// first raise in trace_sync's order to status[i] (null: not wanted).  A raising
+// ray's colour is three quiet NaNs.  Nothing goes to p.err.  Same walk stack
+// as k_tree_finalize (LDS up to 16 levels, private above).  nlev 0: no level
+// ran, every ray was listed (the lanes engine through this entry point).
+template <int SD>
+__global__ __launch_bounds__(256) void k_trace_finalize(KParams p, int nlev, int32_t* status) {
+  __shared__ uint32_t base[LV_MAXL + 1];
+  extern __shared__ uint32_t lds_fin[];
+  uint32_t* pex = lds_fin;
+  lv_layout(p, nlev, base, pex);
+  uint32_t* lo = lds_fin + nlev * 64 + threadIdx.x;
+  uint32_t* hi = lo + SD * 256;
+  uint32_t lo_p[SD > 16 ? LV_MAXL : 1], hi_p[SD > 16 ? LV_MAXL : 1];
+  for (int i = blockIdx.x * 256 + (int)threadIdx.x; i < p.nrays; i += (int)gridDim.x * 256) {
+    uint32_t e = 0, nv = 0;
+    V3 c = SD > 16 ? lv_sample(p, base, pex, i, nlev, lo_p, hi_p, 1, LV_MAXL, e, nv)
+                   : lv_sample(p, base, pex, i, nlev, lo, hi, 256, SD, e, nv);
+    if (e) c.x = c.y = c.z = __builtin_nan("");
+    double* o = p.out + (size_t)i * 3;
+    o[0] = c.x;
+    o[1] = c.y;
+    o[2] = c.z;
+    if (status) status[i] = (int32_t)(e == ERR_TYPE ? 8u : e);   // ERR_ code -> rtx_status (rtx.h)
+  }
+}
+
+// The lanes engine through rtx_trace_device: every ray of the batch is listed
+// for the re-render (k_level_begin has zeroed the list).
+__global__ __launch_bounds__(256) void k_trace_list_all(KParams p) {
+  const int i = blockIdx.x * 256 + (int)threadIdx.x;
+  if (i == 0) p.lv_ctl->redo_n = (uint32_t)p.nrays;
+  if (i >= p.nrays) return;
+  p.lv_redo_of[i] = i;
+  p.lv_redo_list[i] = i;
+}
+
 // The batch's deferred highlight rays (lv_hl_defer): each thread re-runs
 // World#high_lights for one listed ray, now with lit_area_raises for every
 // light that fires (in light order, after that light's own cos raise, as
@@ -1964,6 +2066,20 @@ static void (*level_c_kernel(bool last, int xrm, bool sort))(KParams, int) {
   if (sort) return level_c_xr<SPH, BS, RF, false, true>(xrm);
   return level_c_xr<SPH, BS, RF, false, false>(xrm);
 }
+// The same choice for level 0 of a trace call (k_level_c_rays).
+template <int SPH, int BS, int RF, bool LAST, bool SORT>
+static void (*level_c_rays_xr(int xrm))(KParams, int) {
+  constexpr bool BUF = SPH == SPH_BVH_LDSX || SPH == SPH_BVH_QLDS;
+  if (xrm == XR_NONE) return k_level_c_rays<SPH, BS, RF, LAST, XR_NONE, SORT>;
+  if constexpr (BUF) if (xrm == XR_BUF) return k_level_c_rays<SPH, BS, RF, LAST, XR_BUF, SORT>;
+  return k_level_c_rays<SPH, BS, RF, LAST, XR_WALK, SORT>;
+}
+template <int SPH, int BS, int RF>
+static void (*level_c_rays_kernel(bool last, int xrm, bool sort))(KParams, int) {
+  if (last) return level_c_rays_xr<SPH, BS, RF, true, false>(xrm);
+  if (sort) return level_c_rays_xr<SPH, BS, RF, false, true>(xrm);
+  return level_c_rays_xr<SPH, BS, RF, false, false>(xrm);
+}
 
 static thread_local int64_t* g_plan_out = nullptr;   // set by launch_levels for its first fused launch
 
@@ -1975,9 +2091,11 @@ constexpr int fused_bs() { return RTX_LV_FUSED_BS ? RTX_LV_FUSED_BS : (sph_is_bv
 
 // kind: 0 k_level (fused), 1 k_lv_trace, 2 k_lv_shadow.  Persistent: as many
 // workgroups as fit at once, never more than cap_items need.
+// rays: level 0 of a trace call (fused only): the kernels that read explicit rays.
 template <int SPH, int BS>
 static hipError_t launch_level_bs(const KParams& p, int kind, int level, long cap_items, hipStream_t s,
-                                  KernelEvents* kev) {
+                                  KernelEvents* kev, bool rays = false) {
+  if (rays && (kind != 0 || level != 0)) return hipErrorInvalidValue;
   KParams q = p;
   q.stk_slots_max = 0;                         // no ray stack in this engine
   // the launch plan (rtx_plan.h level_plan): the hit ring, the light buffer and the raise gates in LDS,
@@ -2000,6 +2118,14 @@ static hipError_t launch_level_bs(const KParams& p, int kind, int level, long ca
     const bool last = level == q.lv_last_level, sort = q.lv_sort && level + 1 >= q.lv_sort;
     if (pl.ring_fields == LV_RING_FIELDS) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS>(last, xrm, sort);
     else if (pl.ring_fields == LV_RING_FIELDS_SMALL) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS_SMALL>(last, xrm, sort);
+    if (rays) {
+      kern = xrm == XR_NONE ? k_level_rays<SPH, BS, XR_NONE> : k_level_rays<SPH, BS, XR_WALK>;
+      if (pl.ring_fields == LV_RING_FIELDS) kern = level_c_rays_kernel<SPH, BS, LV_RING_FIELDS>(last, xrm, sort);
+      else if (pl.ring_fields == LV_RING_FIELDS_SMALL)
+        kern = level_c_rays_kernel<SPH, BS, LV_RING_FIELDS_SMALL>(last, xrm, sort);
+    }
+  } else if (rays) {
+    return hipErrorInvalidValue;
   }
   if (kind == 0 && g_plan_out) {               // (launch_levels: the call's first fused launch, as launched)
     *g_plan_out = pack_plan(pl);
@@ -2017,10 +2143,11 @@ static hipError_t launch_level_bs(const KParams& p, int kind, int level, long ca
 // when three of them fit a CU's LDS, else the hierarchy's 512.
 template <int SPH>
 static hipError_t launch_level(const KParams& p, int kind, int level, long cap_items, hipStream_t s,
-                               KernelEvents* kev) {
+                               KernelEvents* kev, bool rays = false) {
   constexpr bool BVH = sph_is_bvh(SPH);
   constexpr int FBS = fused_bs<SPH>();
-  if (kind == 0) return launch_level_bs<SPH, FBS>(p, kind, level, cap_items, s, kev);
+  if (kind == 0) return launch_level_bs<SPH, FBS>(p, kind, level, cap_items, s, kev, rays);
+  if (rays) return hipErrorInvalidValue;
   if (BVH) {
     KParams q = p;
     q.stk_slots_max = 0;
@@ -2031,15 +2158,15 @@ static hipError_t launch_level(const KParams& p, int kind, int level, long cap_i
 }
 
 static hipError_t launch_level_mode(const KParams& p, int mode, int kind, int level, long cap, hipStream_t s,
-                                    KernelEvents* kev) {
+                                    KernelEvents* kev, bool rays = false) {
   switch (mode) {
-    case SPH_LIN_LDS: return launch_level<SPH_LIN_LDS>(p, kind, level, cap, s, kev);
-    case SPH_LIN_SCALAR: return launch_level<SPH_LIN_SCALAR>(p, kind, level, cap, s, kev);
-    case SPH_BVH_LDS: return launch_level<SPH_BVH_LDS>(p, kind, level, cap, s, kev);
-    case SPH_BVH_GLOBAL: return launch_level<SPH_BVH_GLOBAL>(p, kind, level, cap, s, kev);
-    case SPH_BVH_MIX: return launch_level<SPH_BVH_MIX>(p, kind, level, cap, s, kev);
-    case SPH_BVH_LDSX: return launch_level<SPH_BVH_LDSX>(p, kind, level, cap, s, kev);
-    case SPH_BVH_QLDS: return launch_level<SPH_BVH_QLDS>(p, kind, level, cap, s, kev);
+    case SPH_LIN_LDS: return launch_level<SPH_LIN_LDS>(p, kind, level, cap, s, kev, rays);
+    case SPH_LIN_SCALAR: return launch_level<SPH_LIN_SCALAR>(p, kind, level, cap, s, kev, rays);
+    case SPH_BVH_LDS: return launch_level<SPH_BVH_LDS>(p, kind, level, cap, s, kev, rays);
+    case SPH_BVH_GLOBAL: return launch_level<SPH_BVH_GLOBAL>(p, kind, level, cap, s, kev, rays);
+    case SPH_BVH_MIX: return launch_level<SPH_BVH_MIX>(p, kind, level, cap, s, kev, rays);
+    case SPH_BVH_LDSX: return launch_level<SPH_BVH_LDSX>(p, kind, level, cap, s, kev, rays);
+    case SPH_BVH_QLDS: return launch_level<SPH_BVH_QLDS>(p, kind, level, cap, s, kev, rays);
   }
   return hipErrorInvalidValue;
 }
@@ -2100,6 +2227,21 @@ static hipError_t launch_finalize(const KParams& q, int nlev, int n, hipStream_t
   return launch_finalize_sd<64>(q, nlev, n, s);
 }
 
+template <int SD>
+static hipError_t launch_trace_finalize_sd(const KParams& q, int nlev, int32_t* status, hipStream_t s) {
+  const size_t stack = (size_t)nlev * 64 * 4 + (SD > 16 ? 0 : (size_t)SD * 2 * 256 * 4);
+  const long blocks = std::max<long>(1, std::min<long>(((long)q.nrays + 255) / 256, 4096));
+  hipLaunchKernelGGL(k_trace_finalize<SD>, dim3((unsigned)blocks), dim3(256), stack, s, q, nlev, status);
+  return hipGetLastError();
+}
+
+static hipError_t launch_trace_finalize(const KParams& q, int nlev, int32_t* status, hipStream_t s) {
+  if (nlev <= 5) return launch_trace_finalize_sd<4>(q, nlev, status, s);   // (the stacks of launch_finalize)
+  if (nlev <= 8) return launch_trace_finalize_sd<8>(q, nlev, status, s);
+  if (nlev <= 16) return launch_trace_finalize_sd<16>(q, nlev, status, s);
+  return launch_trace_finalize_sd<64>(q, nlev, status, s);
+}
+
 // One batch: reset, the levels, the lanes-engine re-render of overflowed
 // samples (exits at once when there are none), the tree reduction.  A level's
 // launches size their grids for its capacity (level 0: the batch's items;
@@ -2118,6 +2260,8 @@ struct LevelBatch {
   bool first;
   hipEvent_t after_begin;
   int step = 0;
+  bool rays = false;               // a trace call's batch: n0_max explicit rays (q.rays, q.keys, q.nrays), results to
+  int32_t* tr_status = nullptr;    // q.out and tr_status (k_trace_finalize)
   bool done() const { return step > nlev + 1; }
   hipError_t next() {
     hipError_t e = hipSuccess;
@@ -2133,7 +2277,7 @@ struct LevelBatch {
       const long cap = d == 0 ? (long)n0_max : scap;
       if (!q.lv_split) {
         if (q.lv_sort && d >= q.lv_sort) e = launch_bins(q, d, cap, s);
-        if (e == hipSuccess) e = launch_level_mode(q, mode, 0, d, cap, s, kev);
+        if (e == hipSuccess) e = launch_level_mode(q, mode, 0, d, cap, s, kev, rays && d == 0);
       } else {
         const long hits = std::min(cap, hcap);
         e = launch_level_mode(q, mode, 1, d, cap, s, kev);
@@ -2143,8 +2287,9 @@ struct LevelBatch {
       }
     } else {
       e = launch_hl_raise(q, s);
-      if (e == hipSuccess) e = launch_redo(q, mode, maxs, n0_max, s);
-      if (e == hipSuccess && fin_threads > 0) e = launch_finalize(q, nlev, fin_threads, s);
+      if (e == hipSuccess) e = rays ? launch_redo_rays(q, mode, maxs, n0_max, s) : launch_redo(q, mode, maxs, n0_max, s);
+      if (e == hipSuccess && rays) e = launch_trace_finalize(q, nlev, tr_status, s);
+      else if (e == hipSuccess && fin_threads > 0) e = launch_finalize(q, nlev, fin_threads, s);
     }
     step++;
     return e;
@@ -2226,6 +2371,55 @@ hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tile
     q.lv_t0 = q.lv_tiles = 0;
     q.lv_tstride = 1;
     e = level_batch(q, mode, maxs, nlev, q.lv_entries * n_extra, q.lv_entries, s, kev, false);
+  }
+  return e;
+}
+
+// RayTracer#trace_sync for p.nrays explicit rays in device buffers (p.rays,
+// p.keys -> p.out, status), in batches of `batch` rays on stream s (DESIGN.md
+// §3.22).  levels: each batch runs the bounce levels, level 0 reading the
+// explicit rays (k_level_rays / k_level_c_rays), then the deferred highlight
+// checks, the lanes-engine re-trace of the listed rays and the per-ray
+// reduction; split phases are not built for this source (the caller refuses
+// lv_split).  Not levels: every ray is listed and the lanes engine traces the
+// batch.  The lv_* buffers of `p` are the caller's, sized for `batch` level-0
+// items as launch_levels'; the records staged are 96 B (p.lv_ray_dbl = 12).
+hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batch, bool levels, int32_t* status,
+                               hipStream_t s, KernelEvents* kev, int64_t* plan_out) {
+  if (p.nrays <= 0) return hipSuccess;
+  if (levels && (p.lv_split || p.lv_ray_dbl != RAY_DOUBLES)) return hipErrorInvalidValue;
+  struct PlanScope {
+    explicit PlanScope(int64_t* o) { g_plan_out = o; }
+    ~PlanScope() { g_plan_out = nullptr; }
+  } plan_scope(levels ? plan_out : nullptr);
+  mode = resolve_mode(p.scene, mode);
+  batch = std::max(1, std::min(batch, p.nrays));
+  p.tile_order = nullptr;
+  p.lv_pass = 0;
+  p.lv_t0 = p.lv_tiles = p.lv_e0 = p.lv_entries = 0;
+  p.lv_tstride = 1;
+  const KParams whole = p;
+  hipError_t e = hipSuccess;
+  for (int b0 = 0; b0 < whole.nrays && e == hipSuccess; b0 += batch) {
+    KParams q = whole;
+    q.nrays = std::min(batch, whole.nrays - b0);
+    q.rays = whole.rays + (size_t)b0 * 6;
+    q.keys = whole.keys + (size_t)b0 * 3;
+    q.out = whole.out + (size_t)b0 * 3;
+    int32_t* st = status ? status + b0 : nullptr;
+    if (levels) {
+      LevelBatch b{q, mode, maxs, nlev, q.nrays, 0, s, kev, b0 == 0, nullptr};
+      b.rays = true;
+      b.tr_status = st;
+      while (!b.done() && e == hipSuccess) e = b.next();
+      continue;
+    }
+    hipLaunchKernelGGL(k_level_begin, dim3(1), dim3(256), 0, s, q, q.nrays, b0 == 0 ? 1 : 0, 0);
+    hipLaunchKernelGGL(k_trace_list_all, dim3((unsigned)((q.nrays + 255) / 256)), dim3(256), 0, s, q);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = launch_redo_rays(q, mode, maxs, q.nrays, s);
+    q.lv_acc = nullptr;                        // (no level ran: the statistics stay zero)
+    if (e == hipSuccess) e = launch_trace_finalize(q, 0, st, s);
   }
   return e;
 }

@@ -89,13 +89,42 @@ class Renderer:
         self._check(self.lib.rtx_render_at(self.h, x, y, seed, _dp(out)))
         return out
 
-    def trace(self, rays, keys, seed=1):
+    def trace(self, rays, keys, seed=1, check=True):
+        """RayTracer#trace_sync for rays [n, 6] = (front, position) with the RNG keys
+        [n, 3] = (x, y, sample) (rtx_trace) -> colours [n, 3].  check=True raises
+        RtxError for the first raising ray.  check=False returns (colours, status
+        int32 [n]): every ray's own rtx_status, a raising ray's colour NaN, through
+        rtx_trace_device (option "trace_engine"; its default -1 runs the bounce
+        levels here, as 1)."""
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
         keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        if len(keys) != len(rays):
+            raise ValueError("one key per ray")
+        if not check:
+            return self._trace_statuses(rays, keys, seed)
         out = np.empty((len(rays), 3), np.float64)
         self._check(self.lib.rtx_trace(self.h, len(rays), _dp(rays),
                                        keys.ctypes.data_as(C.POINTER(C.c_int32)), seed, _dp(out)))
         return out
+
+    def _trace_statuses(self, rays, keys, seed):
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = len(rays)
+        d_rays, d_keys = torch.tensor(rays, device=dev), torch.tensor(keys, device=dev)   # (copies: read-only arrays too)
+        d_rgb = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        d_status = torch.zeros(n, dtype=torch.int32, device=dev)
+        engine = self.get_option("trace_engine")
+        if engine == -1:
+            self.set_option("trace_engine", 1)
+        try:
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream().cuda_stream
+                self.trace_device(d_rays, d_keys, d_rgb, d_status, seed=seed, stream=stream)
+                return d_rgb.cpu().numpy(), d_status.cpu().numpy()
+        finally:
+            if engine == -1:
+                self.set_option("trace_engine", -1)
 
     def path_trace(self, rays):
         """RayTracer#path_trace_sync for rays [n, 6] = (front, position) -> [n, 3]."""
@@ -262,6 +291,24 @@ class Renderer:
                                                C.c_void_p(d_info or 0), C.c_void_p(d_children or 0),
                                                C.c_void_p(d_child_paths or 0), C.c_void_p(d_leaves or 0),
                                                C.c_void_p(stream or 0)))
+
+    def trace_device(self, d_rays, d_keys, d_rgb, d_status=None, seed=1, stream=None, n=None):
+        """rtx_trace_device: d_rays float64 [n, 6], d_keys int32 [n, 3], d_rgb float64
+        [n, 3], d_status None or int32 [n]: torch tensors on this renderer's device
+        (n = rows of d_rays) or raw device pointers with n given.  Asynchronous on
+        `stream`; raises go to d_status only, a raising ray's colour is NaN."""
+        def ptr(t):
+            return 0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        if n is None:
+            if not hasattr(d_rays, "numel"):
+                raise ValueError("raw device pointers need n")
+            n = d_rays.numel() // 6
+            for t, per in ((d_keys, 3), (d_rgb, 3), (d_status, 1)):
+                if t is not None and hasattr(t, "numel") and t.numel() < n * per:
+                    raise ValueError("a buffer is smaller than the %d rays need" % n)
+        self._check(self.lib.rtx_trace_device(self.h, n, seed, C.c_void_p(ptr(d_rays)), C.c_void_p(ptr(d_keys)),
+                                              C.c_void_p(ptr(d_rgb)), C.c_void_p(ptr(d_status)),
+                                              C.c_void_p(stream or 0)))
 
     def rows_per_rank(self, tile_rows, nranks):
         return self.lib.rtx_tiles_rows_per_rank(self.height, tile_rows, nranks)
