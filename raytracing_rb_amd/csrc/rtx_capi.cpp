@@ -72,29 +72,22 @@ struct rtx_context {
   int64_t opt_tile_order = -1;       // 1: expensive tiles first (k_tile_cost/k_tile_sort), 0: natural order, -1: auto
   int64_t opt_lds_stack = 0;         // ray-stack entries per lane in LDS (-1: as many as fit; 0 measured fastest)
   int64_t opt_engine = 1;            // 0: persistent lanes (per-lane LIFO ray tree), 1: bounce levels (default: faster, same bits)
-  int64_t opt_lv_batch = 1 << 24;    // bounce levels: level-0 items (camera samples) per batch (C4: 2^23 -> 2^24
-                                     // 358.0 -> 352.8 ms, half the level launches and their tails, r08k)
-  int64_t opt_lv_stage_pct = 300;    // bounce levels: ray records per staging buffer, % of the batch items
-  int64_t opt_lv_rec_pct = 1600;      // bounce levels: tree records of a batch (all levels), % of the batch items
-  int64_t opt_lv_floor = 1 << 20;    // bounce levels: at least this many staging and 4x this many tree records
-  int64_t opt_lv_split = PlanOpts{}.lv_split;          // bounce levels: 1 = three phase launches per level (trace / shadow / shade)
+  // (the batch options, their defaults and what each one means: rtx_batch.h BatchOpts)
+  int64_t opt_lv_batch = BatchOpts{}.lv_batch, opt_lv_stage_pct = BatchOpts{}.lv_stage_pct;
+  int64_t opt_lv_rec_pct = BatchOpts{}.lv_rec_pct, opt_lv_floor = BatchOpts{}.lv_floor;
+  int64_t opt_lv_split = BatchOpts{}.lv_split, opt_lv_streams = BatchOpts{}.lv_streams;
+  int64_t opt_lv_ray_bytes = BatchOpts{}.lv_ray_bytes, opt_lv_hl_cap = BatchOpts{}.lv_hl_cap;
+  int64_t opt_lv_sort = BatchOpts{}.lv_sort, opt_lv_sort_from = BatchOpts{}.lv_sort_from;
+  int64_t opt_lv_sort_copy = BatchOpts{}.lv_sort_copy;
   int64_t opt_lv_static = -1;        // bounce levels: % of a launch's chunks scheduled statically (-1 auto)
   int64_t opt_lv_round = -1;         // bounce levels: static chunks in rounds of R per workgroup (0 per wave, -1 auto)
   int64_t opt_lv_compact = PlanOpts{}.lv_compact;       // bounce levels: 1 = park hits in an LDS ring and shade full waves, -1 auto (when it fits)
   int64_t opt_lv_grid_div = 1;       // bounce levels: persistent level grids = resident workgroups / this
   int64_t opt_lv_fin_grid = 0;       // bounce levels: tree reduction blocks per CU (grid-stride over tiles), 0 = one block per tile
   int64_t opt_lv_redo_blocks = 8;    // bounce levels: workgroups of the overflow re-render launch (0: all resident)
-  int64_t opt_lv_streams = 2;        // bounce levels: P = the region's tiles in P interleaved parts on P streams at once
-  int64_t opt_lv_ray_bytes = 0;      // bounce levels: staged ray record, 0 auto (80 B when every path fits 32 bits), 80, 96
-  int64_t opt_lv_hl_cap = 0;         // bounce levels: deferred highlight-check list entries (0 auto)
   int64_t opt_exact_raises = PlanOpts{}.exact_raises;      // 1 (default): local_lights' shadow walks also check the acos raises of the covers they skip
                                      // (§0.0: C2 +3.7 %, C4 +10.4 % against 0)
-  int64_t opt_lv_sort = -1;          // bounce levels: 1 = levels visited bin by bin (direction octant, origin cell), 0 off,
-                                     // -1 auto = on
-  int64_t opt_lv_sort_from = 0;      // bounce levels: the first level binned; 0 auto: level 1 above 512 spheres (C4 354 ->
-                                     // 307 ms), else the last level only (C2 4.60 -> 4.57 ms; all levels 4.65 -> 4.88, r10d/r10k)
   int64_t opt_lv_sort_bits = 0;      // bounce levels: 2^bits origin cells per axis (3 or 4); 0 auto: 4 above 512 spheres, else 3
-  int64_t opt_lv_sort_copy = 0;      // bounce levels: 1 = binning copies the rays' records into bin order (r11i: C4 296 -> 342 ms, off)
   int64_t opt_lbuf = PlanOpts{}.lbuf;              // bounce levels: 1 = shadow walks through the light buffer where it is staged (§3.18)
   int64_t opt_trace_engine = -1;     // explicit rays: 0 lanes, 1 bounce levels, -1 rtx_trace lanes / rtx_trace_device by batch size
   int64_t last_trace_engine = 0;     // the engine the last trace call ran (read-only option trace_engine_last)
@@ -236,11 +229,16 @@ void rtx_context_destroy(rtx_context* c) {
 }
 
 static bool levels_engine(const rtx_context* c);
-static bool lv_paths32(const rtx_context* c);
-static int sph_mode(const rtx_context* c);
+static int levels_sph_mode(const rtx_context* c, int split);
 
-static int lv_sort_from(const rtx_context* c, size_t n0);
-static size_t lv_frame_items(const rtx_context* c);
+static BatchOpts batch_opts(const rtx_context* c) {
+  BatchOpts o;
+  o.lv_batch = c->opt_lv_batch, o.lv_stage_pct = c->opt_lv_stage_pct, o.lv_rec_pct = c->opt_lv_rec_pct;
+  o.lv_floor = c->opt_lv_floor, o.lv_streams = c->opt_lv_streams, o.lv_split = c->opt_lv_split;
+  o.lv_hl_cap = c->opt_lv_hl_cap, o.lv_sort = c->opt_lv_sort, o.lv_sort_from = c->opt_lv_sort_from;
+  o.lv_sort_copy = c->opt_lv_sort_copy, o.lv_ray_bytes = c->opt_lv_ray_bytes;
+  return o;
+}
 
 rtx_status rtx_get_option(rtx_context* c, const char* key, int64_t* value) {
   if (!c || !key || !value) return RTX_EINVAL;
@@ -261,19 +259,22 @@ rtx_status rtx_get_option(rtx_context* c, const char* key, int64_t* value) {
     return RTX_OK;
   }
   if (!strcmp(key, "lv_sort_effective")) {    // read-only: whether the next whole-frame bounce-level render bins its levels
-    *value = c->have_cam && lv_sort_from(c, lv_frame_items(c)) > 0 ? 1 : 0;
+    // the camera samples of a whole-frame render's batch, the frame's tiles split in lv_streams parts
+    // (the default two parts give C2 4,147,200 samples per batch, below the 2^22 of sort_from,
+    // so a single C2 frame bins nothing; the bench's frames in flight render one part of 8.3 M)
+    const BatchOpts o = batch_opts(c);
+    *value = c->have_cam && sort_from(c->scene.n_sphere, c->scene.n_light, c->cam.depth,
+                                      batch_items((int64_t)((c->cam.width + 7) / 8) * ((c->cam.height + 7) / 8),
+                                                  c->cam.pre, c->cam.max_samples, o).n0, o) > 0;
     return RTX_OK;
   }
   if (!strcmp(key, "sph_mode_effective")) {   // read-only: the SphMode of the next bounce-level render's walks
     if (!c->have_scene) return fail(c, RTX_EINVAL, "sph_mode_effective: no scene uploaded");
-    const int m = c->opt_sphere_src == -1
-                      ? levels_auto_mode(c->scene, sph_mode(c), (int)c->opt_lv_compact, (int)c->opt_lv_split)
-                      : sph_mode(c);
-    *value = resolve_mode(c->scene, m);
+    *value = resolve_mode(c->scene, levels_sph_mode(c, (int)c->opt_lv_split));
     return RTX_OK;
   }
   if (!strcmp(key, "lv_ray_bytes_effective")) {   // read-only: the staged ray record of the next level render
-    *value = c->opt_lv_ray_bytes == 96 || (c->have_cam && !lv_paths32(c)) ? 96 : 80;
+    *value = c->opt_lv_ray_bytes == 96 || (c->have_cam && !lv_paths32(c->cam.depth, c->cam.pt)) ? 96 : 80;
     return RTX_OK;
   }
   const struct { const char* k; int64_t v; } tab[] = {
@@ -604,54 +605,7 @@ static rtx_status prep(rtx_context* c, KParams& p, uint64_t seed) {
   return RTX_OK;
 }
 
-// launch_render with its per-launch sample records and extra-sample list,
-// allocated stream-ordered (the device's default pool keeps the memory, so
-// after the first frame this costs no hipMalloc) and freed after the launch,
-// so launches of one context on different streams never share them.
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// The bounce-level engine can take this camera: its levels and child slots.
-// 80-B ray records when a ray's path id fits 32 bits at every level: path
-// < (pt + 3)^trace_depth (the path ids of rtx_device.h emit / lv_finish).
-// lv_ray_bytes 80 asked for a camera whose paths do not fit is refused, not
-// truncated.
-static bool lv_paths32(const rtx_context* c) {
-  uint64_t v = 1;
-  for (int l = 0; l < c->cam.depth; l++) {
-    v *= (uint64_t)c->cam.pt + 3;
-    if (v > (1ull << 32)) return false;
-  }
-  return true;
-}
-
-// ray binning (option lv_sort) for the fused level launches
-// The first level binned (0: none) and the bins' resolution.  Large scenes
-// bin every level >= 1 (C4 354 -> 307 ms); small ones only the last, where the
-// rays are most incoherent and most numerous (C2: binning every level costs
-// more than it gains, r10d; the last level alone gains 0.5 %, r10k).
-// n0: the camera samples of a batch (the last level of a small scene is binned
-// only from 2^22 of them: a 1/8 or 1/4 share of the C2 frame lost 4-5 % to the
-// binning passes' fixed cost, half of it neither gained nor lost, r10p).
-static int lv_sort_from(const rtx_context* c, size_t n0) {
-  const bool split = c->opt_lv_split != 0 && c->scene.n_light <= LV_SPLIT_MAX_LIGHTS;
-  if (c->opt_lv_sort == 0 || split) return 0;
-  const bool large = c->scene.n_sphere > 512;
-  if (c->opt_lv_sort == -1 && c->opt_lv_sort_from == 0 && !large && n0 < ((size_t)1 << 22)) return 0;
-  const int from = c->opt_lv_sort_from > 0 ? (int)c->opt_lv_sort_from : large ? 1 : c->cam.depth - 1;
-  return from >= 1 && from < c->cam.depth ? from : 0;
-}
-// the camera samples of a whole-frame render's batch (lv_sort_effective): the
-// arithmetic of render_levels' n0, with the frame's tiles split in lv_streams
-// parts (the default two parts give C2 4,147,200 samples per batch,
-// below the 2^22 of lv_sort_from, so a single C2 frame bins nothing; the
-// bench's frames in flight render one part of 8.3 M)
-static size_t lv_frame_items(const rtx_context* c) {
-  const int64_t tiles = (int64_t)((c->cam.width + 7) / 8) * ((c->cam.height + 7) / 8);
-  const int64_t per_tile = 64 * (int64_t)std::max(1, c->cam.pre);
-  const int64_t parts = std::max<int64_t>(1, std::min<int64_t>(c->opt_lv_streams, tiles));
-  const int64_t batch_tiles = std::max<int64_t>(1, std::min<int64_t>(c->opt_lv_batch / per_tile, (tiles + parts - 1) / parts));
-  return std::max<size_t>((size_t)(batch_tiles * per_tile), (size_t)std::max(0, c->cam.max_samples - c->cam.pre));
-}
+// (al256, the batch arithmetic, lv_paths32 and sort_from: rtx_batch.h)
 static int lv_sort_bits(const rtx_context* c) {
   return c->opt_lv_sort_bits ? (int)c->opt_lv_sort_bits : c->scene.n_sphere > 512 ? 4 : 3;
 }
@@ -662,97 +616,77 @@ static bool levels_fit(const rtx_context* c) {
 }
 static bool levels_engine(const rtx_context* c) { return c->opt_engine == 1 && levels_fit(c); }
 
-// render_region for the bounce-level engine (DESIGN.md §3.7): batches of
-// 8x8 tiles, one launch per tree level, the trees reduced by k_tree_finalize.
-// Buffers for one batch, stream-ordered from the device pool like the lanes
-// engine's: staging (2 x lv_stage_pct % of the batch items x 96 B), tree
-// records (lv_rec_pct % x 32 B with one light), the re-render list.
-static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_t stream) {
-  const size_t npx = (size_t)p.nx * p.nrows;
-  const int tiles = ((p.nx + 7) / 8) * ((p.nrows + 7) / 8);
-  const int per_tile = 64 * p.pre;
-  const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(c->opt_lv_streams, tiles));   // lv_streams (below)
-  const int batch_tiles =
-      (int)std::max<int64_t>(1, std::min<int64_t>(c->opt_lv_batch / per_tile, (tiles + parts - 1) / parts));
-  // level-0 items of one batch: pass 0 (tiles) or pass 1 (>= one pixel's extra samples)
-  const size_t n0 = std::max((size_t)batch_tiles * per_tile, (size_t)std::max(0, p.max_samples - p.pre));
-  const size_t fl = (size_t)c->opt_lv_floor;
-  const size_t want = std::max<size_t>(std::max<size_t>(64, fl), n0 * (size_t)c->opt_lv_stage_pct / 100);
-  const size_t lcap = std::max<size_t>(std::max(n0, 4 * fl), n0 * (size_t)c->opt_lv_rec_pct / 100);
-  // queues of levels >= 1: LV_SLICES slices of 2^k slots (k rounded up)
-  int slog2 = 0;
-  while (((size_t)LV_SLICES << slog2) < want) slog2++;
-  const size_t scap = (size_t)LV_SLICES << slog2;
-  if (scap > UINT32_MAX / 2 || lcap > UINT32_MAX / 2)
-    return fail(c, RTX_EINVAL, "bounce-level buffers exceed 2^31 records: lower lv_batch");
-  const bool path32 = lv_paths32(c);
-  if (c->opt_lv_ray_bytes == 80 && !path32)
-    return fail(c, RTX_EINVAL, "lv_ray_bytes 80: this camera's ray paths need 64 bits ((pt + 3)^trace_depth > 2^32)");
-  const int rec_bytes = levels_rec_bytes(c->scene.n_light);
-  // deferred highlight checks (k_hl_raise): room for 1/256 of the batch's tree
-  // records (rays; C2 fires on ~0.1 % of them); a ray that finds the list full
-  // has its sample re-rendered by the lanes engine (option lv_hl_cap: the size)
-  const size_t hlcap = c->opt_lv_hl_cap > 0 ? (size_t)c->opt_lv_hl_cap : std::max<size_t>(4096, lcap / 256);
-  const size_t sz_hlq = al256(hlcap * 64);
-  const size_t sz_ctl = al256(sizeof(LevelCtl)), sz_redo = al256(n0 * 4), sz_smp = al256(n0 * 32),
-               sz_stage = al256(scap * RAY_BYTES), sz_rec = al256(lcap * (size_t)rec_bytes),
-               sz_extra = al256((npx + 64) * 4);
-  // split phases: the hit queue of a level (at most its rays) and its shadow results
-  const bool split = c->opt_lv_split != 0 && c->scene.n_light <= LV_SPLIT_MAX_LIGHTS;
-  int hlog2 = 0;
-  while (((size_t)LV_SLICES << hlog2) < std::max(n0, scap)) hlog2++;
-  const size_t hcap = (size_t)LV_SLICES << hlog2;
-  const size_t sz_hit = split ? al256(hcap * LV_HIT_BYTES) : 0,
-               sz_area = split ? al256(hcap * (size_t)std::max(1, c->scene.n_light) * 16) : 0;
-  // ray binning (lv_sort, fused levels only): a bin per staged slot, the
-  // level's bin list, the bin counts and cursors
-  const int sort_from = lv_sort_from(c, n0);
-  const bool sort = sort_from > 0;
-  c->last_sort_levels = sort ? std::max(0, c->cam.depth - sort_from) : 0;   // (read-only option lv_sort_last)
+// ------------------------------------------------------------------ what the launching calls share
+// The event pairs around a call's ray-tree kernel launches (option "kernel_events"), created on first use.
+static rtx_status kernel_events(rtx_context* c, bool on, KernelEvents& kev) {
+  kev = KernelEvents{c->ev, 0, rtx_context::MAX_EV};
+  if (on && !c->ev[0])
+    for (int k = 0; k < 2 * rtx_context::MAX_EV; k++) HIPCHK(c, hipEventCreate(&c->ev[k]));
+  return RTX_OK;
+}
+
+// After a call's launches (status e): the pairs it recorded are the context's, and its buffer goes back
+// to the pool in stream order whether the launches succeeded or not.
+static rtx_status launched(rtx_context* c, hipError_t e, const KernelEvents* kev, void* buf, hipStream_t stream) {
+  if (kev) c->n_ev = kev->n;
+  const hipError_t f = hipFreeAsync(buf, stream);
+  HIPCHK(c, e);
+  HIPCHK(c, f);
+  return RTX_OK;
+}
+
+// The sphere mode of a bounce-level call's walks (before resolve_mode).
+// sphere_src auto: C4-sized hierarchies keep their nodes and 16-bit leaf
+// records in LDS next to the hit rings (SPH_BVH_QLDS; before round 4 the
+// leaves came from global memory, SPH_BVH_MIX, r05b: C4 410 -> 386 ms)
+static int levels_sph_mode(const rtx_context* c, int split) {
+  return c->opt_sphere_src == -1 ? levels_auto_mode(c->scene, sph_mode(c), (int)c->opt_lv_compact, split) : sph_mode(c);
+}
+
+// The layout of a bounce-level call's buffers (rtx_batch.h) for this context's scene, camera and options.
+static BatchLayout context_layout(const rtx_context* c, bool trace, bool levels, size_t n0, int parts, size_t npx) {
+  return batch_layout(BatchIn{trace, levels, n0, parts, npx, c->scene.n_sphere, c->scene.n_light, c->cam.depth, c->cam.pt},
+                      batch_opts(c));
+}
+
+// The buffers of one part's set at `base` (rtx_batch.h: a buffer the layout leaves out is a null pointer).
+static void carve(KParams& k, char* base, const BatchLayout& L) {
+  auto at = [&](BatchBuf b) { return L.present[b] ? base + L.off[b] : nullptr; };
+  k.lv_ctl = (LevelCtl*)at(LB_CTL);
+  k.lv_redo_of = (int32_t*)at(LB_REDO_OF);
+  k.lv_redo_list = (int32_t*)at(LB_REDO_LIST);
+  k.lv_redo_smp = (double*)at(LB_REDO_SMP);
+  k.lv_stage[0] = (double*)at(LB_STAGE0);
+  k.lv_stage[1] = (double*)at(LB_STAGE1);
+  k.lv_rec = at(LB_REC);
+  k.lv_hit = (double*)at(LB_HIT);
+  k.lv_area = (double*)at(LB_AREA);
+  k.lv_hlq = (double*)at(LB_HLQ);
+  k.lv_key = (uint16_t*)at(LB_KEY);
+  k.lv_perm = (uint2*)at(LB_PERM);
+  k.lv_bins = (uint32_t*)at(LB_BINS);
+  k.lv_sorted = (double*)at(LB_SORTED);
+}
+
+// A bounce-level call's buffer (stream-ordered from the device pool like the
+// lanes engine's, `parts` sets and the tail) and the level fields of `p` that
+// do not depend on which entry the call came through.
+static rtx_status level_params(rtx_context* c, KParams& p, const BatchLayout& L, int parts, hipStream_t stream,
+                               char*& buf) {
+  if (L.refusal) return fail(c, RTX_EINVAL, "%s", L.refusal);
+  c->last_sort_levels = L.sort_from > 0 ? std::max(0, c->cam.depth - L.sort_from) : 0;   // (read-only option lv_sort_last)
   c->last_plan = -1;                           // (read-only option lv_plan_last: set by the first fused launch)
-  const size_t sz_key = sort ? al256(scap * 2) : 0, sz_perm = sort ? al256(scap * 8) : 0,
-               sz_bins = sort ? al256((size_t)LV_BINS * 8) : 0;
-  // One buffer set per part: with lv_streams = P the region's tiles are
-  // rendered in P interleaved parts at once, parts 1.. on the context's aux
-  // streams (one part's level tails, launch gaps and reductions overlap the
-  // others' levels).  The extra-sample list and the statistics are shared
-  // (appended / added atomically); each part has its own level buffers, its
-  // own lanes-engine work counter and ray stacks for its overflow re-render.
-  // (lv_sort_copy: the binned level's records in bin order, a third staging buffer)
-  const bool sort_copy = sort && c->opt_lv_sort_copy == 1;
-  const size_t sz_sorted = sort_copy ? sz_stage : 0;
-  const size_t set = sz_ctl + 2 * sz_redo + sz_smp + 2 * sz_stage + sz_rec + sz_hit + sz_area + sz_hlq + sz_key +
-                     sz_perm + sz_bins + sz_sorted;
-  const size_t total = parts * set + sz_extra;
   if (!c->d_lvstats) HIPCHK(c, hipMalloc(&c->d_lvstats, sizeof(unsigned long long) * (LV_MAXL + 3)));
-  char* buf = nullptr;
-  HIPCHK(c, hipMallocAsync((void**)&buf, total, stream));
-  auto carve = [&](KParams& k, char* q) {
-    k.lv_ctl = (LevelCtl*)q;                  q += sz_ctl;
-    k.lv_redo_of = (int32_t*)q;               q += sz_redo;
-    k.lv_redo_list = (int32_t*)q;             q += sz_redo;
-    k.lv_redo_smp = (double*)q;               q += sz_smp;
-    k.lv_stage[0] = (double*)q;               q += sz_stage;
-    k.lv_stage[1] = (double*)q;               q += sz_stage;
-    k.lv_rec = q;                             q += sz_rec;
-    k.lv_hit = split ? (double*)q : nullptr;  q += sz_hit;
-    k.lv_area = split ? (double*)q : nullptr; q += sz_area;
-    k.lv_hlq = (double*)q;                    q += sz_hlq;
-    k.lv_hlq_cap = (uint32_t)hlcap;
-    k.lv_key = sort ? (uint16_t*)q : nullptr;      q += sz_key;
-    k.lv_perm = sort ? (uint2*)q : nullptr;        q += sz_perm;
-    k.lv_bins = sort ? (uint32_t*)q : nullptr;     q += sz_bins;
-    k.lv_sorted = sort_copy ? (double*)q : nullptr; q += sz_sorted;
-    k.lv_sort = sort_from;
-    k.lv_cell_bits = lv_sort_bits(c);
-    k.lv_lbuf = (int32_t)c->opt_lbuf;
-  };
-  carve(p, buf);
-  p.lv_split = split ? 1 : 0;
+  HIPCHK(c, hipMallocAsync((void**)&buf, L.total, stream));
+  carve(p, buf, L);
+  p.extra_count = (int32_t*)(buf + parts * L.set);   // the tail (the first batch's k_level_begin zeroes the count)
+  p.lv_hlq_cap = (uint32_t)L.hlcap;
+  p.lv_sort = L.sort_from;
+  p.lv_cell_bits = lv_sort_bits(c);
+  p.lv_lbuf = (int32_t)c->opt_lbuf;
+  p.lv_split = L.split ? 1 : 0;
   p.lv_compact = (int32_t)c->opt_lv_compact;
   p.lv_grid_div = (int32_t)c->opt_lv_grid_div;
-  p.lv_redo_blocks = (int32_t)c->opt_lv_redo_blocks;
-  p.lv_fin_tiles = (int32_t)c->opt_lv_fin_grid;   // (blocks per CU here; the launcher sets the tile count)
   // Static chunks cost no atomics; dynamic claims balance rays of very
   // different cost.  Auto: all static while the sphere records fit one walk
   // workgroup's LDS with room to spare (C2: 5.35 vs 5.9 ms at 50 %), half
@@ -764,17 +698,37 @@ static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_
   // 32 above (C4 31.53 -> 31.95 Mpix/s; 8: 31.72).
   p.lv_round = c->opt_lv_round >= 0 ? (int32_t)c->opt_lv_round : (c->scene.n_sphere <= 512 ? 8 : 32);
   p.lds_sched = -1;
-  p.extra_count = (int32_t*)(buf + parts * set);
-  p.extra_list = p.extra_count + 64;
-  p.lv_scap = (uint32_t)scap;
-  p.lv_slice_log2 = slog2;
-  p.lv_hslice_log2 = hlog2;
-  p.lv_lcap = (uint32_t)lcap;
-  p.lv_rec_bytes = rec_bytes;
-  p.lv_ray_dbl = (c->opt_lv_ray_bytes == 96 || !path32) ? 12 : 10;
+  p.lv_scap = (uint32_t)L.scap;
+  p.lv_slice_log2 = L.slog2;
+  p.lv_hslice_log2 = L.hlog2;
+  p.lv_lcap = (uint32_t)L.lcap;
+  p.lv_rec_bytes = L.rec_bytes;
+  p.lv_ray_dbl = L.ray_dbl;
   p.lv_last_level = c->cam.depth >= 1 ? c->cam.depth - 1 : -1;
   p.lv_acc = c->d_lvstats;
   p.samples = nullptr;
+  return RTX_OK;
+}
+
+// render_region for the bounce-level engine (DESIGN.md §3.7): batches of
+// 8x8 tiles, one launch per tree level, the trees reduced by k_tree_finalize.
+// Buffers for one batch: staging (2 x lv_stage_pct % of the batch items x
+// 96 B), tree records (lv_rec_pct % x 32 B with one light), the re-render list.
+static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_t stream) {
+  const BatchItems it = batch_items(((p.nx + 7) / 8) * ((p.nrows + 7) / 8), p.pre, p.max_samples, batch_opts(c));
+  // One buffer set per part: with lv_streams = P the region's tiles are
+  // rendered in P interleaved parts at once, parts 1.. on the context's aux
+  // streams (one part's level tails, launch gaps and reductions overlap the
+  // others' levels).  The extra-sample list and the statistics are shared
+  // (appended / added atomically); each part has its own level buffers, its
+  // own lanes-engine work counter and ray stacks for its overflow re-render.
+  const int parts = it.parts;
+  const BatchLayout L = context_layout(c, false, true, it.n0, parts, (size_t)p.nx * p.nrows);
+  char* buf = nullptr;
+  if (rtx_status s = level_params(c, p, L, parts, stream, buf)) return s;
+  p.extra_list = p.extra_count + 64;
+  p.lv_redo_blocks = (int32_t)c->opt_lv_redo_blocks;
+  p.lv_fin_tiles = (int32_t)c->opt_lv_fin_grid;   // (blocks per CU here; the launcher sets the tile count)
   LvAux aux{};
   if (parts > 1) {
     aux.parts = parts;
@@ -793,31 +747,25 @@ static rtx_status render_levels(rtx_context* c, KParams& p, int maxs, hipStream_
       }
       KParams& q = aux.pb[j];
       q = p;
-      carve(q, buf + (size_t)(j + 1) * set);
+      carve(q, buf + (size_t)(j + 1) * L.set, L);
       q.work = reinterpret_cast<int*>(&q.lv_ctl->pad[0]);   // zeroed by its part's k_level_begin
       q.stk_glb = c->d_stk2[j];
       aux.s2[j] = c->aux[j];
       aux.ev_done[j] = c->lv_ev[j + 1];
     }
   }
-  KernelEvents kev{c->ev, 0, rtx_context::MAX_EV};
-  if (c->opt_kernel_events && !c->ev[0])
-    for (int k = 0; k < 2 * rtx_context::MAX_EV; k++) HIPCHK(c, hipEventCreate(&c->ev[k]));
-  // sphere_src auto: C4-sized hierarchies keep their nodes and 16-bit leaf
-  // records in LDS next to the hit rings (SPH_BVH_QLDS; before round 4 the
-  // leaves came from global memory, SPH_BVH_MIX, r05b: C4 410 -> 386 ms)
-  const int mode = c->opt_sphere_src == -1 ? levels_auto_mode(c->scene, sph_mode(c), (int)c->opt_lv_compact,
-                                                              (int)c->opt_lv_split)
-                                           : sph_mode(c);
-  const hipError_t e = launch_levels(p, mode, maxs, std::max(1, c->cam.depth), batch_tiles, stream,
-                                     c->opt_kernel_events ? &kev : nullptr, parts > 1 ? &aux : nullptr, &c->last_plan);
-  if (c->opt_kernel_events) c->n_ev = kev.n;
-  const hipError_t f = hipFreeAsync(buf, stream);
-  HIPCHK(c, e);
-  HIPCHK(c, f);
-  return RTX_OK;
+  KernelEvents kev;
+  if (rtx_status s = kernel_events(c, c->opt_kernel_events != 0, kev)) return s;
+  KernelEvents* const ke = c->opt_kernel_events ? &kev : nullptr;
+  const hipError_t e = launch_levels(p, levels_sph_mode(c, (int)c->opt_lv_split), maxs, std::max(1, c->cam.depth),
+                                     it.batch_tiles, stream, ke, parts > 1 ? &aux : nullptr, &c->last_plan);
+  return launched(c, e, ke, buf, stream);
 }
 
+// launch_render with its per-launch sample records and extra-sample list,
+// allocated stream-ordered (the device's default pool keeps the memory, so
+// after the first frame this costs no hipMalloc) and freed after the launch,
+// so launches of one context on different streams never share them.
 static rtx_status render_region(rtx_context* c, KParams& p, bool count, int maxs, hipStream_t stream) {
   const size_t npx = (size_t)p.nx * p.nrows;
   if (npx == 0) return RTX_OK;
@@ -845,17 +793,10 @@ static rtx_status render_region(rtx_context* c, KParams& p, bool count, int maxs
   // gains nothing (the frame is 500 ms of evenly expensive tiles).
   const bool order = c->opt_tile_order > 0 || (c->opt_tile_order < 0 && c->scene.n_sphere <= RTX_TILE_ORDER_SPHERES);
   p.tile_order = order ? p.tile_cls + tiles : nullptr;
-  KernelEvents kev{c->ev, 0, rtx_context::MAX_EV};
-  if (c->opt_kernel_events && !count && !c->ev[0]) {
-    for (int k = 0; k < 2 * rtx_context::MAX_EV; k++) HIPCHK(c, hipEventCreate(&c->ev[k]));
-  }
-  const hipError_t e = launch_render(p, sph_mode(c), count, maxs, stream,
-                                     c->opt_kernel_events && !count ? &kev : nullptr);
-  if (c->opt_kernel_events && !count) c->n_ev = kev.n;
-  const hipError_t f = hipFreeAsync(buf, stream);
-  HIPCHK(c, e);
-  HIPCHK(c, f);
-  return RTX_OK;
+  KernelEvents kev;
+  if (rtx_status s = kernel_events(c, c->opt_kernel_events && !count, kev)) return s;
+  KernelEvents* const ke = c->opt_kernel_events && !count ? &kev : nullptr;
+  return launched(c, launch_render(p, sph_mode(c), count, maxs, stream, ke), ke, buf, stream);
 }
 
 rtx_status rtx_render_device(rtx_context* c, int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint64_t seed,
@@ -1637,86 +1578,23 @@ rtx_status rtx_render_at(rtx_context* c, int32_t x, int32_t y, uint64_t seed, do
 #define RTX_TRACE_LEVELS_MIN_RAYS 64
 #endif
 
-// One trace call on `stream`: the batch buffers (stream-ordered from the
-// device pool, as render_levels'; one part), then launch_trace_levels.  Buffer
-// sizing is render_levels' with "camera samples" read as "rays"; the staged
-// records are always 96 B (the 80-B record decodes the RNG key from a camera
-// item, which an explicit ray is not), whatever "lv_ray_bytes" says.
+// One trace call on `stream`: the batch buffers (level_params, as a render's,
+// with "camera samples" read as "rays"; one part), then launch_trace_levels.
+// The staged records are always 96 B, whatever "lv_ray_bytes" says.
 static rtx_status trace_levels(rtx_context* c, KParams& p, int maxs, bool levels, int32_t* d_status,
                                hipStream_t stream) {
-  const size_t n0 = (size_t)std::max<int64_t>(1, std::min<int64_t>(c->opt_lv_batch, p.nrays));
-  const size_t fl = (size_t)c->opt_lv_floor;
-  const size_t want = std::max<size_t>(std::max<size_t>(64, fl), n0 * (size_t)c->opt_lv_stage_pct / 100);
-  const size_t lcap = std::max<size_t>(std::max(n0, 4 * fl), n0 * (size_t)c->opt_lv_rec_pct / 100);
-  int slog2 = 0;
-  while (((size_t)LV_SLICES << slog2) < want) slog2++;
-  const size_t scap = (size_t)LV_SLICES << slog2;
-  if (levels && (scap > UINT32_MAX / 2 || lcap > UINT32_MAX / 2))
-    return fail(c, RTX_EINVAL, "bounce-level buffers exceed 2^31 records: lower lv_batch");
-  const int rec_bytes = levels_rec_bytes(c->scene.n_light);
-  const size_t hlcap = c->opt_lv_hl_cap > 0 ? (size_t)c->opt_lv_hl_cap : std::max<size_t>(4096, lcap / 256);
-  const int sort_from = levels ? lv_sort_from(c, n0) : 0;
-  const bool sort = sort_from > 0, sort_copy = sort && c->opt_lv_sort_copy == 1;
-  const size_t sz_ctl = al256(sizeof(LevelCtl)), sz_redo = al256(n0 * 4), sz_smp = al256(n0 * 32),
-               sz_stage = levels ? al256(scap * RAY_BYTES) : 0, sz_rec = levels ? al256(lcap * (size_t)rec_bytes) : 0,
-               sz_hlq = levels ? al256(hlcap * 64) : 0, sz_key = sort ? al256(scap * 2) : 0,
-               sz_perm = sort ? al256(scap * 8) : 0, sz_bins = sort ? al256((size_t)LV_BINS * 8) : 0,
-               sz_sorted = sort_copy ? sz_stage : 0;
-  const size_t total = sz_ctl + 2 * sz_redo + sz_smp + 2 * sz_stage + sz_rec + sz_hlq + sz_key + sz_perm + sz_bins +
-                       sz_sorted + 256;
-  if (!c->d_lvstats) HIPCHK(c, hipMalloc(&c->d_lvstats, sizeof(unsigned long long) * (LV_MAXL + 3)));
+  const size_t n0 = trace_items(p.nrays, batch_opts(c));
   char* buf = nullptr;
-  HIPCHK(c, hipMallocAsync((void**)&buf, total, stream));
-  char* q = buf;
-  p.lv_ctl = (LevelCtl*)q;                  q += sz_ctl;
-  p.lv_redo_of = (int32_t*)q;               q += sz_redo;
-  p.lv_redo_list = (int32_t*)q;             q += sz_redo;
-  p.lv_redo_smp = (double*)q;               q += sz_smp;
-  p.lv_stage[0] = (double*)q;               q += sz_stage;
-  p.lv_stage[1] = (double*)q;               q += sz_stage;
-  p.lv_rec = q;                             q += sz_rec;
-  p.lv_hlq = levels ? (double*)q : nullptr; q += sz_hlq;
-  p.lv_hlq_cap = levels ? (uint32_t)hlcap : 0;
-  p.lv_key = sort ? (uint16_t*)q : nullptr;       q += sz_key;
-  p.lv_perm = sort ? (uint2*)q : nullptr;         q += sz_perm;
-  p.lv_bins = sort ? (uint32_t*)q : nullptr;      q += sz_bins;
-  p.lv_sorted = sort_copy ? (double*)q : nullptr; q += sz_sorted;
-  p.extra_count = (int32_t*)q;                 // (k_level_begin zeroes it)
-  p.lv_sort = sort_from;
-  p.lv_cell_bits = lv_sort_bits(c);
-  p.lv_lbuf = (int32_t)c->opt_lbuf;
-  p.lv_split = 0;
-  p.lv_compact = (int32_t)c->opt_lv_compact;
-  p.lv_grid_div = (int32_t)c->opt_lv_grid_div;
+  if (rtx_status s = level_params(c, p, context_layout(c, true, levels, n0, 1, 0), 1, stream, buf)) return s;
   // the levels' overflow re-trace keeps the render's grid cap; the lanes engine takes every resident workgroup
   p.lv_redo_blocks = levels ? (int32_t)c->opt_lv_redo_blocks : 0;
-  p.lv_static_pct = c->opt_lv_static >= 0 ? (int32_t)c->opt_lv_static : (c->scene.n_sphere <= 512 ? 100 : 50);
-  p.lv_round = c->opt_lv_round >= 0 ? (int32_t)c->opt_lv_round : (c->scene.n_sphere <= 512 ? 8 : 32);
-  p.lds_sched = -1;
-  p.lv_scap = (uint32_t)scap;
-  p.lv_slice_log2 = slog2;
-  p.lv_hslice_log2 = 0;
-  p.lv_lcap = (uint32_t)lcap;
-  p.lv_rec_bytes = rec_bytes;
-  p.lv_ray_dbl = 12;
-  p.lv_last_level = c->cam.depth >= 1 ? c->cam.depth - 1 : -1;
-  p.lv_acc = c->d_lvstats;
-  p.samples = nullptr;
-  c->last_sort_levels = sort ? std::max(0, c->cam.depth - sort_from) : 0;
-  c->last_plan = -1;
-  KernelEvents kev{c->ev, 0, rtx_context::MAX_EV};
-  if (c->opt_kernel_events && !c->ev[0])
-    for (int k = 0; k < 2 * rtx_context::MAX_EV; k++) HIPCHK(c, hipEventCreate(&c->ev[k]));
-  const int mode = c->opt_sphere_src == -1 ? levels_auto_mode(c->scene, sph_mode(c), (int)c->opt_lv_compact, 0)
-                                           : sph_mode(c);
-  const hipError_t e = launch_trace_levels(p, levels ? mode : sph_mode(c), maxs, std::max(1, c->cam.depth), (int)n0,
-                                           levels, d_status, stream, c->opt_kernel_events ? &kev : nullptr,
+  KernelEvents kev;
+  if (rtx_status s = kernel_events(c, c->opt_kernel_events != 0, kev)) return s;
+  KernelEvents* const ke = c->opt_kernel_events ? &kev : nullptr;
+  const hipError_t e = launch_trace_levels(p, levels ? levels_sph_mode(c, 0) : sph_mode(c), maxs,
+                                           std::max(1, c->cam.depth), (int)n0, levels, d_status, stream, ke,
                                            &c->last_plan);
-  if (c->opt_kernel_events) c->n_ev = kev.n;
-  const hipError_t f = hipFreeAsync(buf, stream);
-  HIPCHK(c, e);
-  HIPCHK(c, f);
-  return RTX_OK;
+  return launched(c, e, ke, buf, stream);
 }
 
 rtx_status rtx_trace_device(rtx_context* c, int32_t n, uint64_t seed, const double* d_rays, const int32_t* d_keys,

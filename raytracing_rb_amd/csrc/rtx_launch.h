@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rtx_batch.h"
 #include "rtx_plan.h"
 #include "rtx_scene.h"
 
@@ -17,36 +18,7 @@ struct ErrState {
   unsigned long long first[5];     // per ERR_ code (rtx_vec3.h): min key (pixels: (x*H + y)*2 + phase, render_sync order; rays: index)
 };
 
-// Bounce-level engine: one launch per tree level (or three,
-// option lv_split).  The ray queue of every level >= 1 (and the hit queue of
-// the split phases) is cut into LV_SLICES slices of 2^k slots, each with its
-// own allocation counter on its own 128-B line (no contended device atomics).
-constexpr int LV_MAXL = 64;                     // levels (= trace_depth) the engine supports
-constexpr int LV_SLICES = 64;                   // slices per queue (one per lane of a consumer wave)
-constexpr int LV_CLAIMS = 16;                   // sharded chunk-claim counters per launch
-constexpr int LV_DONE = 16;                     // wave-completion counters per level launch (lv_level_done)
-constexpr int LV_CELL_BITS_MAX = 4;             // ray bins (option lv_sort): origin cells per axis = 2^lv_cell_bits
-constexpr int LV_BINS = 8 << (3 * LV_CELL_BITS_MAX); // x 8 direction octants: at most 32,768 bins
-}  // namespace rtx
-#include "rtx_sched.h"                          // LV_ROUND_MAX, lv_static_chunks, lv_round_chunk (host and device)
-namespace rtx {
-struct LevelCtl {
-  uint32_t count0;                              // level-0 items of the batch
-  uint32_t redo_n;                              // level-0 items handed to the lanes engine (capacity overflow)
-  uint32_t dropped;                             // child rays that found no room (diagnostic)
-  uint32_t hl_n;                                // highlight rays whose lit_area raise check is deferred (k_hl_raise)
-  uint32_t pad[27];                             // (pad[0]: the lanes-engine work counter of parts 1..)
-  uint32_t sc[LV_MAXL + 1][LV_SLICES * 32];     // rays allocated in slice s of level d: sc[d][32 s]
-  uint32_t sh[LV_MAXL + 1][LV_SLICES * 32];     // split phases: hits of level d in slice s
-  uint32_t claim[3][LV_MAXL + 1][LV_CLAIMS * 32]; // chunk claims: [launch kind: fused/trace, shadow, shade][level][j * 32]
-  // compact layout of level d (written by the last workgroup of the launch that allocated it)
-  uint32_t lay_cnt[LV_MAXL + 2][LV_SLICES];     // rays in slice s (clamped to the slice)
-  uint32_t lay_pex[LV_MAXL + 2][LV_SLICES];     // exclusive ray prefix of slice s
-  uint32_t lay_cin[LV_MAXL + 2][LV_SLICES];     // inclusive 64-ray chunk prefix of slice s
-  uint32_t lay_base[LV_MAXL + 2];               // first record of level d in the arena
-  uint32_t done[LV_MAXL + 2];                   // completed done_sub counters of the launch allocating level d
-  uint32_t done_sub[LV_MAXL + 1][LV_DONE * 32]; // finished waves w (w mod LV_DONE = j) of that launch: [d][32 j]
-};
+// (LV_MAXL, LV_SLICES, ..., LevelCtl, RAY_BYTES, levels_rec_bytes and the batch layout: rtx_batch.h, host-only)
 
 struct KParams {
   SceneDev scene;                  // by value: read by scalar loads from the kernarg segment
@@ -167,7 +139,6 @@ hipError_t launch_trace(KParams p, int mode, int maxs, hipStream_t s);
 // statistics shared with `p`).  The parts j > 0 start after the first reset
 // on `s` (ev_first); `s` waits for all of them (ev_done) before the extra
 // samples (pass 1), which run on `s` alone.
-constexpr int LV_MAX_PARTS = 4;
 struct LvAux {
   int parts;                       // P (2 .. LV_MAX_PARTS)
   KParams pb[LV_MAX_PARTS - 1];
@@ -177,10 +148,6 @@ struct LvAux {
 hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tiles, hipStream_t s,
                          KernelEvents* kev = nullptr, const LvAux* aux = nullptr, int64_t* plan_out = nullptr);
 // (plan_out: receives rtx_plan.h pack_plan of the call's first fused level launch, as launched)
-// Tree-record bytes for a scene with n_light lights (one leaf per fired light).
-int levels_rec_bytes(int n_light);
-constexpr size_t RAY_BYTES = 96;                // staged ray record of the bounce-level engine (at most)
-constexpr size_t LV_HIT_BYTES = 64;             // split phases: hit-queue record
 hipError_t launch_path_trace(KParams p, hipStream_t s);
 // The lanes engine's re-render of the level-0 items listed in lv_redo_list
 // (SRC_LIST; exits at once when the list is empty).

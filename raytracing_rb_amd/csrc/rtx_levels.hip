@@ -2,6 +2,7 @@
 // RayTracer#trace_sync (src/ray_tracer.rb:16-46) breadth-first, one launch per
 // ray-tree level (or three: trace / shadow / shade), and Camera#render_at's
 // reduction over the stored trees.
+#include <type_traits>
 #include <vector>
 
 #include "rtx_device.h"
@@ -159,11 +160,6 @@ struct LvStamps {
 #endif
   }
 };
-
-int levels_rec_bytes(int n_light) {
-  const int nl = n_light > 1 ? n_light : 1;
-  return (8 + 24 * nl + 15) & ~15;       // {meta, first child} + one leaf per fired light
-}
 
 // slice counter of slice s of a level (own 128-B line)
 __device__ __forceinline__ uint32_t* lv_slice_ctr(uint32_t* level_ctrs, int s) { return level_ctrs + s * 32; }
@@ -655,7 +651,8 @@ __device__ __forceinline__ bool lv_walk(const KParams& p, char* lds, bool ext, V
 // LSRC_RAYS: ray `idx` of an explicit batch (rtx_trace_device):
 // p.rays[idx] with the RNG key p.keys[idx]; items past p.nrays are padding.
 // Only the level-0 kernels of a trace call are instantiated for it
-// (k_level_rays, k_level_c_rays): every other kernel compiles from LSRC_CAMERA.
+// (k_level / k_level_c <..., LSRC_RAYS>, picked by launch_level_bs): every
+// other kernel compiles from LSRC_CAMERA.
 enum { LSRC_CAMERA = 0, LSRC_RAYS = 1 };
 __device__ __forceinline__ void lv_ray_explicit(const KParams& p, uint32_t idx, Ray& r, int& x, int& y, int& sample) {
   const double* q = p.rays + (size_t)idx * 6;
@@ -1012,18 +1009,14 @@ __device__ __forceinline__ void k_level_body(const KParams& p, int level) {
   st.flush(level);
 }
 
-template <int SPH, int BS, int XR>
+// SRC = LSRC_RAYS: level 0 of a trace call (rtx_trace_device), the batch's
+// explicit rays.  The level is then a constant, so the staged-child arms of
+// the body fold away.
+template <int SPH, int BS, int XR, int SRC = LSRC_CAMERA>
 __global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level(KParams p, int level) {
-  k_level_body<SPH, BS, XR>(p, level);
+  if constexpr (SRC == LSRC_RAYS) level = 0;
+  k_level_body<SPH, BS, XR, SRC>(p, level);
   lv_level_done(p, level + 1);
-}
-
-// Level 0 of a trace call (rtx_trace_device): the batch's explicit rays.  The
-// level is a constant, so the staged-child arms of the body fold away.
-template <int SPH, int BS, int XR>
-__global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level_rays(KParams p, int) {
-  k_level_body<SPH, BS, XR, LSRC_RAYS>(p, 0);
-  lv_level_done(p, 1);
 }
 
 // ----------------------------------------------------------------- hit compaction
@@ -1280,17 +1273,11 @@ __device__ __forceinline__ void k_level_c_body(const KParams& p, int level) {
   st.flush(level);
 }
 
-template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
+template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT, int SRC = LSRC_CAMERA>
 __global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level_c(KParams p, int level) {
-  k_level_c_body<SPH, BS, RF, LAST, XR, SORT>(p, level);
+  if constexpr (SRC == LSRC_RAYS) level = 0;   // (as k_level)
+  k_level_c_body<SPH, BS, RF, LAST, XR, SORT, SRC>(p, level);
   lv_level_done(p, level + 1);
-}
-
-// k_level_c for level 0 of a trace call (see k_level_rays).
-template <int SPH, int BS, int RF, bool LAST, int XR, bool SORT>
-__global__ __launch_bounds__(BS, RTX_LVL_WPS) void k_level_c_rays(KParams p, int) {
-  k_level_c_body<SPH, BS, RF, LAST, XR, SORT, LSRC_RAYS>(p, 0);
-  lv_level_done(p, 1);
 }
 
 // ----------------------------------------------------------------- split phases
@@ -2048,40 +2035,44 @@ static hipError_t launch_timed(K kern, long blocks, int bs, size_t lds, hipStrea
   return e;
 }
 
+// What a level launch is asked for, besides the batch's parameters.
+struct LevelLaunch {
+  int kind;                        // 0 k_level / k_level_c (fused), 1 k_lv_trace, 2 k_lv_shadow
+  int level;
+  long cap_items;                  // persistent: as many workgroups as fit at once, never more than these need
+  hipStream_t s;
+  KernelEvents* kev;
+  bool rays;                       // level 0 of a trace call: the kernels that read explicit rays (fused, level 0 only)
+  int64_t** plan;                  // *plan: where the call's first fused launch records its plan as launched
+                                   // (rtx_plan.h pack_plan; cleared by that launch), or null
+};
+using LevelKernel = void (*)(KParams, int);
+
 // k_level_c for a level: the batch's last level compiled apart; with ray
 // binning (lv_sort) the other levels write their children's bins (SORT: a
 // kernel of its own, the key's registers would cost the default one spills).
 // xrm: XR_NONE / XR_BUF / XR_WALK (lv_walk); XR_BUF is instantiated only for
 // the sphere modes with a light buffer (the others take XR_WALK).
-template <int SPH, int BS, int RF, bool LAST, bool SORT>
-static void (*level_c_xr(int xrm))(KParams, int) {
+template <int SPH, int BS, int RF, bool LAST, bool SORT, int SRC>
+static LevelKernel level_c_xr(int xrm) {
   constexpr bool BUF = SPH == SPH_BVH_LDSX || SPH == SPH_BVH_QLDS;
-  if (xrm == XR_NONE) return k_level_c<SPH, BS, RF, LAST, XR_NONE, SORT>;
-  if constexpr (BUF) if (xrm == XR_BUF) return k_level_c<SPH, BS, RF, LAST, XR_BUF, SORT>;
-  return k_level_c<SPH, BS, RF, LAST, XR_WALK, SORT>;
+  if (xrm == XR_NONE) return k_level_c<SPH, BS, RF, LAST, XR_NONE, SORT, SRC>;
+  if constexpr (BUF) if (xrm == XR_BUF) return k_level_c<SPH, BS, RF, LAST, XR_BUF, SORT, SRC>;
+  return k_level_c<SPH, BS, RF, LAST, XR_WALK, SORT, SRC>;
 }
-template <int SPH, int BS, int RF>
-static void (*level_c_kernel(bool last, int xrm, bool sort))(KParams, int) {
-  if (last) return level_c_xr<SPH, BS, RF, true, false>(xrm);
-  if (sort) return level_c_xr<SPH, BS, RF, false, true>(xrm);
-  return level_c_xr<SPH, BS, RF, false, false>(xrm);
+template <int SPH, int BS, int RF, int SRC>
+static LevelKernel level_c_kernel(bool last, int xrm, bool sort) {
+  if (last) return level_c_xr<SPH, BS, RF, true, false, SRC>(xrm);
+  if (sort) return level_c_xr<SPH, BS, RF, false, true, SRC>(xrm);
+  return level_c_xr<SPH, BS, RF, false, false, SRC>(xrm);
 }
-// The same choice for level 0 of a trace call (k_level_c_rays).
-template <int SPH, int BS, int RF, bool LAST, bool SORT>
-static void (*level_c_rays_xr(int xrm))(KParams, int) {
-  constexpr bool BUF = SPH == SPH_BVH_LDSX || SPH == SPH_BVH_QLDS;
-  if (xrm == XR_NONE) return k_level_c_rays<SPH, BS, RF, LAST, XR_NONE, SORT>;
-  if constexpr (BUF) if (xrm == XR_BUF) return k_level_c_rays<SPH, BS, RF, LAST, XR_BUF, SORT>;
-  return k_level_c_rays<SPH, BS, RF, LAST, XR_WALK, SORT>;
+// The fused kernel of a plan: k_level_c with the plan's ring (hit compaction), k_level without one.
+template <int SPH, int BS, int SRC>
+static LevelKernel fused_kernel(const LevelPlan& pl, bool last, bool sort) {
+  if (pl.ring_fields == LV_RING_FIELDS) return level_c_kernel<SPH, BS, LV_RING_FIELDS, SRC>(last, pl.xrm, sort);
+  if (pl.ring_fields == LV_RING_FIELDS_SMALL) return level_c_kernel<SPH, BS, LV_RING_FIELDS_SMALL, SRC>(last, pl.xrm, sort);
+  return pl.xrm == XR_NONE ? k_level<SPH, BS, XR_NONE, SRC> : k_level<SPH, BS, XR_WALK, SRC>;
 }
-template <int SPH, int BS, int RF>
-static void (*level_c_rays_kernel(bool last, int xrm, bool sort))(KParams, int) {
-  if (last) return level_c_rays_xr<SPH, BS, RF, true, false>(xrm);
-  if (sort) return level_c_rays_xr<SPH, BS, RF, false, true>(xrm);
-  return level_c_rays_xr<SPH, BS, RF, false, false>(xrm);
-}
-
-static thread_local int64_t* g_plan_out = nullptr;   // set by launch_levels for its first fused launch
 
 #ifndef RTX_LV_FUSED_BS
 #define RTX_LV_FUSED_BS 0                  // k_level's block size (0: BS_LIN / BS_BVH)
@@ -2089,84 +2080,67 @@ static thread_local int64_t* g_plan_out = nullptr;   // set by launch_levels for
 template <int SPH>
 constexpr int fused_bs() { return RTX_LV_FUSED_BS ? RTX_LV_FUSED_BS : (sph_is_bvh(SPH) ? BS_BVH : BS_LIN); }
 
-// kind: 0 k_level (fused), 1 k_lv_trace, 2 k_lv_shadow.  Persistent: as many
-// workgroups as fit at once, never more than cap_items need.
-// rays: level 0 of a trace call (fused only): the kernels that read explicit rays.
 template <int SPH, int BS>
-static hipError_t launch_level_bs(const KParams& p, int kind, int level, long cap_items, hipStream_t s,
-                                  KernelEvents* kev, bool rays = false) {
-  if (rays && (kind != 0 || level != 0)) return hipErrorInvalidValue;
+static hipError_t launch_level_bs(const KParams& p, const LevelLaunch& a) {
+  constexpr bool FUSED_BS = BS == fused_bs<SPH>();
+  // explicit rays are a source of the fused kernel's level 0 alone (the only kernels compiled for LSRC_RAYS)
+  if (a.rays && (a.kind != 0 || a.level != 0 || !FUSED_BS)) return hipErrorInvalidValue;
   KParams q = p;
   q.stk_slots_max = 0;                         // no ray stack in this engine
   // the launch plan (rtx_plan.h level_plan): the hit ring, the light buffer and the raise gates in LDS,
   // the raise check's variant, the workgroup's claim counter and the dynamic LDS bytes
   const PlanIn in{q.lv_compact, q.lv_lbuf, q.exact_raises, q.scene.lbuf != nullptr, q.scene.rbuf != nullptr};
-  const LevelPlan pl = level_plan(q.scene, in, SPH, BS, BS == fused_bs<SPH>(), kind);
+  const LevelPlan pl = level_plan(q.scene, in, SPH, BS, FUSED_BS, a.kind);
   apply_walk_lds(q, pl.walk);
-  const size_t lds = pl.lds;
   if (pl.ring_fields) q.lds_ring = pl.lds_ring;
   q.lds_lbuf = pl.lds_lbuf;
   q.lds_rgate = pl.lds_rgate;
   if (pl.lds_sched >= 0) q.lds_sched = pl.lds_sched;
   else q.lv_round = 0;                         // no room for the counter: the per-wave static schedule
-  const int xrm = pl.xrm;
   // k_level_c (hit compaction) is instantiated for the fused kernel's block size only; XR_BUF only for
   // the sphere modes with a light buffer (level_c_xr)
-  auto kern = kind == 0 ? (xrm == XR_NONE ? k_level<SPH, BS, XR_NONE> : k_level<SPH, BS, XR_WALK>)
-              : kind == 1 ? k_lv_trace<SPH, BS> : k_lv_shadow<SPH, BS>;
-  if constexpr (BS == fused_bs<SPH>()) {
-    const bool last = level == q.lv_last_level, sort = q.lv_sort && level + 1 >= q.lv_sort;
-    if (pl.ring_fields == LV_RING_FIELDS) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS>(last, xrm, sort);
-    else if (pl.ring_fields == LV_RING_FIELDS_SMALL) kern = level_c_kernel<SPH, BS, LV_RING_FIELDS_SMALL>(last, xrm, sort);
-    if (rays) {
-      kern = xrm == XR_NONE ? k_level_rays<SPH, BS, XR_NONE> : k_level_rays<SPH, BS, XR_WALK>;
-      if (pl.ring_fields == LV_RING_FIELDS) kern = level_c_rays_kernel<SPH, BS, LV_RING_FIELDS>(last, xrm, sort);
-      else if (pl.ring_fields == LV_RING_FIELDS_SMALL)
-        kern = level_c_rays_kernel<SPH, BS, LV_RING_FIELDS_SMALL>(last, xrm, sort);
-    }
-  } else if (rays) {
-    return hipErrorInvalidValue;
+  LevelKernel kern = a.kind == 0   ? (pl.xrm == XR_NONE ? k_level<SPH, BS, XR_NONE> : k_level<SPH, BS, XR_WALK>)
+                     : a.kind == 1 ? k_lv_trace<SPH, BS>
+                                   : k_lv_shadow<SPH, BS>;
+  if constexpr (FUSED_BS) {
+    const bool last = a.level == q.lv_last_level, sort = q.lv_sort && a.level + 1 >= q.lv_sort;
+    if (a.kind == 0)
+      kern = a.rays ? fused_kernel<SPH, BS, LSRC_RAYS>(pl, last, sort) : fused_kernel<SPH, BS, LSRC_CAMERA>(pl, last, sort);
   }
-  if (kind == 0 && g_plan_out) {               // (launch_levels: the call's first fused launch, as launched)
-    *g_plan_out = pack_plan(pl);
-    g_plan_out = nullptr;
+  if (a.kind == 0 && a.plan && *a.plan) {      // the call's first fused launch
+    **a.plan = pack_plan(pl);
+    *a.plan = nullptr;
   }
   int cus = 0, per_cu = 0;                     // (also raises the kernel's dynamic-LDS limit once)
-  const hipError_t e = cus_and_fit(reinterpret_cast<const void*>(kern), BS, lds, cus, per_cu);
+  const hipError_t e = cus_and_fit(reinterpret_cast<const void*>(kern), BS, pl.lds, cus, per_cu);
   if (e != hipSuccess) return e;
   const long grid = std::max<long>(1, (long)cus * per_cu / std::max(1, q.lv_grid_div));
-  return launch_timed(kern, std::min<long>((cap_items + BS - 1) / BS, grid), BS, lds, s, kev, q, level);
+  return launch_timed(kern, std::min<long>((a.cap_items + BS - 1) / BS, grid), BS, pl.lds, a.s, a.kev, q, a.level);
 }
 
 // The fused kernel runs the engine's block sizes (BS_LIN / BS_BVH, 2 waves per
 // SIMD).  The split walk kernels (3 waves per SIMD) take 256-thread blocks
 // when three of them fit a CU's LDS, else the hierarchy's 512.
 template <int SPH>
-static hipError_t launch_level(const KParams& p, int kind, int level, long cap_items, hipStream_t s,
-                               KernelEvents* kev, bool rays = false) {
-  constexpr bool BVH = sph_is_bvh(SPH);
-  constexpr int FBS = fused_bs<SPH>();
-  if (kind == 0) return launch_level_bs<SPH, FBS>(p, kind, level, cap_items, s, kev, rays);
-  if (rays) return hipErrorInvalidValue;
-  if (BVH) {
+static hipError_t launch_level(const KParams& p, const LevelLaunch& a) {
+  if (a.kind == 0) return launch_level_bs<SPH, fused_bs<SPH>()>(p, a);
+  if (sph_is_bvh(SPH)) {
     KParams q = p;
     q.stk_slots_max = 0;
-    if (3 * lds_layout(q, SPH, 256) > LDS_TOTAL_BYTES)
-      return launch_level_bs<SPH, BS_BVH>(p, kind, level, cap_items, s, kev);
+    if (3 * lds_layout(q, SPH, 256) > LDS_TOTAL_BYTES) return launch_level_bs<SPH, BS_BVH>(p, a);
   }
-  return launch_level_bs<SPH, 256>(p, kind, level, cap_items, s, kev);
+  return launch_level_bs<SPH, 256>(p, a);
 }
 
-static hipError_t launch_level_mode(const KParams& p, int mode, int kind, int level, long cap, hipStream_t s,
-                                    KernelEvents* kev, bool rays = false) {
+static hipError_t launch_level_mode(const KParams& p, int mode, const LevelLaunch& a) {
   switch (mode) {
-    case SPH_LIN_LDS: return launch_level<SPH_LIN_LDS>(p, kind, level, cap, s, kev, rays);
-    case SPH_LIN_SCALAR: return launch_level<SPH_LIN_SCALAR>(p, kind, level, cap, s, kev, rays);
-    case SPH_BVH_LDS: return launch_level<SPH_BVH_LDS>(p, kind, level, cap, s, kev, rays);
-    case SPH_BVH_GLOBAL: return launch_level<SPH_BVH_GLOBAL>(p, kind, level, cap, s, kev, rays);
-    case SPH_BVH_MIX: return launch_level<SPH_BVH_MIX>(p, kind, level, cap, s, kev, rays);
-    case SPH_BVH_LDSX: return launch_level<SPH_BVH_LDSX>(p, kind, level, cap, s, kev, rays);
-    case SPH_BVH_QLDS: return launch_level<SPH_BVH_QLDS>(p, kind, level, cap, s, kev, rays);
+    case SPH_LIN_LDS: return launch_level<SPH_LIN_LDS>(p, a);
+    case SPH_LIN_SCALAR: return launch_level<SPH_LIN_SCALAR>(p, a);
+    case SPH_BVH_LDS: return launch_level<SPH_BVH_LDS>(p, a);
+    case SPH_BVH_GLOBAL: return launch_level<SPH_BVH_GLOBAL>(p, a);
+    case SPH_BVH_MIX: return launch_level<SPH_BVH_MIX>(p, a);
+    case SPH_BVH_LDSX: return launch_level<SPH_BVH_LDSX>(p, a);
+    case SPH_BVH_QLDS: return launch_level<SPH_BVH_QLDS>(p, a);
   }
   return hipErrorInvalidValue;
 }
@@ -2197,50 +2171,51 @@ static hipError_t launch_bins(const KParams& q, int level, long cap, hipStream_t
   return hipGetLastError();
 }
 
-template <int SD>
-static hipError_t launch_finalize_sd(const KParams& q, int nlev, int n, hipStream_t s) {
-  const size_t stack = (size_t)nlev * 64 * 4 + (SD > 16 ? 0 : (size_t)SD * 2 * 256 * 4);
-  if (q.lv_pass == 0) {                        // n = tiles of the batch
-    const size_t lds = ((stack + 7) & ~(size_t)7) + (size_t)64 * q.pre * 28;
-    KParams r = q;
-    long grid = n;
-    if (q.lv_fin_tiles > 0) {                  // lv_fin_grid blocks per CU, grid-stride over the tiles
-      int dev = 0, cus = 0;
-      if (hipGetDevice(&dev) == hipSuccess &&
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-        grid = std::min<long>(n, (long)cus * q.lv_fin_tiles);
-    }
-    r.lv_fin_tiles = n;
-    hipLaunchKernelGGL(k_tree_finalize<SD>, dim3((unsigned)grid), dim3(256), lds, s, r, nlev);
-  } else {                                     // n = extra-list entries of the batch
-    hipLaunchKernelGGL(k_tree_finalize_extra<SD>, dim3((unsigned)((n + 255) / 256)), dim3(256), stack, s, q, nlev);
-  }
-  return hipGetLastError();
+// The reductions' walk stack depth SD for trees of nlev levels, handed to `f` as a constant (f(sd, stack),
+// sd() == SD; stack: the dynamic LDS bytes of the walk's stacks).  A walk keeps one pending child range per
+// level below the root: nlev - 1 entries; the smaller stack lets 8 blocks share a CU (C2, depth 5) instead of 6.
+template <typename F>
+static hipError_t with_stack_depth(int nlev, F f) {
+  auto call = [&](auto sd) {
+    constexpr int SD = decltype(sd)::value;
+    return f(sd, (size_t)nlev * 64 * 4 + (SD > 16 ? 0 : (size_t)SD * 2 * 256 * 4));
+  };
+  if (nlev <= 5) return call(std::integral_constant<int, 4>{});
+  if (nlev <= 8) return call(std::integral_constant<int, 8>{});
+  if (nlev <= 16) return call(std::integral_constant<int, 16>{});
+  return call(std::integral_constant<int, 64>{});
 }
 
 static hipError_t launch_finalize(const KParams& q, int nlev, int n, hipStream_t s) {
-  // a walk keeps one pending child range per level below the root: nlev - 1
-  // entries; the smaller stack lets 8 blocks share a CU (C2, depth 5) instead of 6
-  if (nlev <= 5) return launch_finalize_sd<4>(q, nlev, n, s);
-  if (nlev <= 8) return launch_finalize_sd<8>(q, nlev, n, s);
-  if (nlev <= 16) return launch_finalize_sd<16>(q, nlev, n, s);
-  return launch_finalize_sd<64>(q, nlev, n, s);
-}
-
-template <int SD>
-static hipError_t launch_trace_finalize_sd(const KParams& q, int nlev, int32_t* status, hipStream_t s) {
-  const size_t stack = (size_t)nlev * 64 * 4 + (SD > 16 ? 0 : (size_t)SD * 2 * 256 * 4);
-  const long blocks = std::max<long>(1, std::min<long>(((long)q.nrays + 255) / 256, 4096));
-  hipLaunchKernelGGL(k_trace_finalize<SD>, dim3((unsigned)blocks), dim3(256), stack, s, q, nlev, status);
-  return hipGetLastError();
+  return with_stack_depth(nlev, [&](auto sd, size_t stack) {
+    constexpr int SD = decltype(sd)::value;
+    if (q.lv_pass == 0) {                      // n = tiles of the batch
+      const size_t lds = ((stack + 7) & ~(size_t)7) + (size_t)64 * q.pre * 28;
+      KParams r = q;
+      long grid = n;
+      if (q.lv_fin_tiles > 0) {                // lv_fin_grid blocks per CU, grid-stride over the tiles
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+          grid = std::min<long>(n, (long)cus * q.lv_fin_tiles);
+      }
+      r.lv_fin_tiles = n;
+      hipLaunchKernelGGL(k_tree_finalize<SD>, dim3((unsigned)grid), dim3(256), lds, s, r, nlev);
+    } else {                                   // n = extra-list entries of the batch
+      hipLaunchKernelGGL(k_tree_finalize_extra<SD>, dim3((unsigned)((n + 255) / 256)), dim3(256), stack, s, q, nlev);
+    }
+    return hipGetLastError();
+  });
 }
 
 static hipError_t launch_trace_finalize(const KParams& q, int nlev, int32_t* status, hipStream_t s) {
-  if (nlev <= 5) return launch_trace_finalize_sd<4>(q, nlev, status, s);   // (the stacks of launch_finalize)
-  if (nlev <= 8) return launch_trace_finalize_sd<8>(q, nlev, status, s);
-  if (nlev <= 16) return launch_trace_finalize_sd<16>(q, nlev, status, s);
-  return launch_trace_finalize_sd<64>(q, nlev, status, s);
+  return with_stack_depth(nlev, [&](auto sd, size_t stack) {
+    const long blocks = std::max<long>(1, std::min<long>(((long)q.nrays + 255) / 256, 4096));
+    hipLaunchKernelGGL(k_trace_finalize<decltype(sd)::value>, dim3((unsigned)blocks), dim3(256), stack, s, q, nlev, status);
+    return hipGetLastError();
+  });
 }
+
 
 // One batch: reset, the levels, the lanes-engine re-render of overflowed
 // samples (exits at once when there are none), the tree reduction.  A level's
@@ -2259,10 +2234,16 @@ struct LevelBatch {
   KernelEvents* kev;
   bool first;
   hipEvent_t after_begin;
+  int64_t** plan;                  // (LevelLaunch::plan: one per call, shared by its batches)
   int step = 0;
   bool rays = false;               // a trace call's batch: n0_max explicit rays (q.rays, q.keys, q.nrays), results to
   int32_t* tr_status = nullptr;    // q.out and tr_status (k_trace_finalize)
   bool done() const { return step > nlev + 1; }
+  hipError_t run() {                 // every step, in order
+    hipError_t e = hipSuccess;
+    while (!done() && e == hipSuccess) e = next();
+    return e;
+  }
   hipError_t next() {
     hipError_t e = hipSuccess;
     if (step == 0) {
@@ -2277,12 +2258,12 @@ struct LevelBatch {
       const long cap = d == 0 ? (long)n0_max : scap;
       if (!q.lv_split) {
         if (q.lv_sort && d >= q.lv_sort) e = launch_bins(q, d, cap, s);
-        if (e == hipSuccess) e = launch_level_mode(q, mode, 0, d, cap, s, kev, rays && d == 0);
+        if (e == hipSuccess) e = launch_level_mode(q, mode, LevelLaunch{0, d, cap, s, kev, rays && d == 0, plan});
       } else {
         const long hits = std::min(cap, hcap);
-        e = launch_level_mode(q, mode, 1, d, cap, s, kev);
+        e = launch_level_mode(q, mode, LevelLaunch{1, d, cap, s, kev, false, nullptr});
         if (e == hipSuccess && q.scene.n_light > 0)
-          e = launch_level_mode(q, mode, 2, d, hits * q.scene.n_light, s, kev);
+          e = launch_level_mode(q, mode, LevelLaunch{2, d, hits * q.scene.n_light, s, kev, false, nullptr});
         if (e == hipSuccess) e = launch_shade(q, d, hits, s, kev);
       }
     } else {
@@ -2296,26 +2277,24 @@ struct LevelBatch {
   }
 };
 
-static hipError_t level_batch(KParams q, int mode, int maxs, int nlev, int n0_max, int fin_threads, hipStream_t s,
-                              KernelEvents* kev, bool first, hipEvent_t after_begin = nullptr) {
-  LevelBatch b{q, mode, maxs, nlev, n0_max, fin_threads, s, kev, first, after_begin};
-  hipError_t e = hipSuccess;
-  while (!b.done() && e == hipSuccess) e = b.next();
-  return e;
+// What a call of the engine settles before its first batch: the sphere mode
+// its launches run, no tile order, and batch fields that name nothing yet.
+static void begin_call(KParams& p, int& mode) {
+  mode = resolve_mode(p.scene, mode);
+  p.tile_order = nullptr;
+  p.lv_pass = 0;
+  p.lv_t0 = p.lv_tiles = p.lv_e0 = p.lv_entries = 0;
+  p.lv_tstride = 1;
 }
 
 hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tiles, hipStream_t s,
                          KernelEvents* kev, const LvAux* aux, int64_t* plan_out) {
   const int tiles = ((p.nx + 7) / 8) * ((p.nrows + 7) / 8);
   if (tiles == 0) return hipSuccess;
-  struct PlanScope {                           // (cleared on every way out: a call of split phases records none)
-    explicit PlanScope(int64_t* o) { g_plan_out = o; }
-    ~PlanScope() { g_plan_out = nullptr; }
-  } plan_scope(plan_out);
-  mode = resolve_mode(p.scene, mode);
+  begin_call(p, mode);
+  int64_t* plan = plan_out;                    // (a call of split phases records none)
   batch_tiles = std::max(1, std::min(batch_tiles, tiles));
   const int per_tile = 64 * p.pre;
-  p.tile_order = nullptr;
   if (aux && tiles < aux->parts) aux = nullptr;
   // The parts interleave tiles (tile t in part t mod P): neighbouring tiles
   // cost alike, so the parts are balanced and each one's tail overlaps the
@@ -2340,7 +2319,7 @@ hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tile
       q.lv_e0 = q.lv_entries = 0;
       const bool first = j == 0 && k0 == 0;
       seq[j].push_back(LevelBatch{q, mode, maxs, nlev, q.lv_tiles * per_tile, q.lv_tiles, st, kev, first,
-                                  first && aux ? aux->ev_first : nullptr});
+                                  first && aux ? aux->ev_first : nullptr, &plan});
     }
   }
   std::vector<size_t> at(parts, 0);
@@ -2368,9 +2347,7 @@ hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tile
     q.lv_pass = 1;
     q.lv_e0 = e0;
     q.lv_entries = std::min(entries, npx - e0);
-    q.lv_t0 = q.lv_tiles = 0;
-    q.lv_tstride = 1;
-    e = level_batch(q, mode, maxs, nlev, q.lv_entries * n_extra, q.lv_entries, s, kev, false);
+    e = LevelBatch{q, mode, maxs, nlev, q.lv_entries * n_extra, q.lv_entries, s, kev, false, nullptr, &plan}.run();
   }
   return e;
 }
@@ -2378,26 +2355,20 @@ hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tile
 // RayTracer#trace_sync for p.nrays explicit rays in device buffers (p.rays,
 // p.keys -> p.out, status), in batches of `batch` rays on stream s (DESIGN.md
 // §3.22).  levels: each batch runs the bounce levels, level 0 reading the
-// explicit rays (k_level_rays / k_level_c_rays), then the deferred highlight
+// explicit rays (k_level / k_level_c <..., LSRC_RAYS>), then the deferred highlight
 // checks, the lanes-engine re-trace of the listed rays and the per-ray
 // reduction; split phases are not built for this source (the caller refuses
 // lv_split).  Not levels: every ray is listed and the lanes engine traces the
-// batch.  The lv_* buffers of `p` are the caller's, sized for `batch` level-0
-// items as launch_levels'; the records staged are 96 B (p.lv_ray_dbl = 12).
+// batch (no plan is recorded).  The lv_* buffers of `p` are the caller's, sized
+// for `batch` level-0 items as launch_levels'; the records staged are 96 B
+// (p.lv_ray_dbl = 12).
 hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batch, bool levels, int32_t* status,
                                hipStream_t s, KernelEvents* kev, int64_t* plan_out) {
   if (p.nrays <= 0) return hipSuccess;
   if (levels && (p.lv_split || p.lv_ray_dbl != RAY_DOUBLES)) return hipErrorInvalidValue;
-  struct PlanScope {
-    explicit PlanScope(int64_t* o) { g_plan_out = o; }
-    ~PlanScope() { g_plan_out = nullptr; }
-  } plan_scope(levels ? plan_out : nullptr);
-  mode = resolve_mode(p.scene, mode);
+  begin_call(p, mode);
+  int64_t* plan = plan_out;
   batch = std::max(1, std::min(batch, p.nrays));
-  p.tile_order = nullptr;
-  p.lv_pass = 0;
-  p.lv_t0 = p.lv_tiles = p.lv_e0 = p.lv_entries = 0;
-  p.lv_tstride = 1;
   const KParams whole = p;
   hipError_t e = hipSuccess;
   for (int b0 = 0; b0 < whole.nrays && e == hipSuccess; b0 += batch) {
@@ -2408,10 +2379,10 @@ hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batc
     q.out = whole.out + (size_t)b0 * 3;
     int32_t* st = status ? status + b0 : nullptr;
     if (levels) {
-      LevelBatch b{q, mode, maxs, nlev, q.nrays, 0, s, kev, b0 == 0, nullptr};
+      LevelBatch b{q, mode, maxs, nlev, q.nrays, 0, s, kev, b0 == 0, nullptr, &plan};
       b.rays = true;
       b.tr_status = st;
-      while (!b.done() && e == hipSuccess) e = b.next();
+      e = b.run();
       continue;
     }
     hipLaunchKernelGGL(k_level_begin, dim3(1), dim3(256), 0, s, q, q.nrays, b0 == 0 ? 1 : 0, 0);
@@ -2423,5 +2394,6 @@ hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batc
   }
   return e;
 }
+
 
 }  // namespace rtx

@@ -12,10 +12,21 @@
 // options (rtx_plan.h fused_plan, the arithmetic the launcher runs; the read-only option
 // lv_plan_last reports the same integer after a render) and the scalars it depends on;
 // "status <code> <message>" for a world the host build refuses (tests/test_level_plans.py).
+//
+// scene_dump --buffers [case...]: no world; per case (an argument, or a line of stdin when
+// there is no argument) one line of "name value" pairs with the batch and the buffer layout
+// of a bounce-level call (rtx_batch.h batch_items / trace_items / batch_layout, the arithmetic
+// rtx_capi.cpp runs) and sizeof(LevelCtl) (tests/test_level_buffers.py).  A case is 21
+// integers: trace (0 render, 1 trace), the region's 8x8 tiles (render), its pixels or the
+// call's rays, pre, max_samples, trace_depth, pt, n_sphere, n_light, levels (0: a trace call
+// through the lanes engine), then BatchOpts' fields in their order: lv_batch lv_stage_pct
+// lv_rec_pct lv_floor lv_streams lv_split lv_hl_cap lv_sort lv_sort_from lv_sort_copy
+// lv_ray_bytes.  A refusal's message is printed with '_' for its spaces ("-": none).
 #include <stdio.h>
 #include <string.h>
 
 #include "../raytracing_rb_amd/cli/scene_load.hpp"
+#include "../raytracing_rb_amd/csrc/rtx_batch.h"
 #include "../raytracing_rb_amd/csrc/rtx_plan.h"
 #include "../raytracing_rb_amd/csrc/rtx_scene_build.h"
 
@@ -55,12 +66,59 @@ static int plans(int n, char** worlds) {
   return 0;
 }
 
+// One --buffers case -> one line of "name value" pairs: the level-0 items of a batch and the layout of
+// the call's buffers (rtx_batch.h), as rtx_capi.cpp asks for them.
+static int buffers_case(const char* text) {
+  long long v[21];
+  int n = 0, used = 0;
+  for (const char* q = text; n < 21 && sscanf(q, "%lld%n", &v[n], &used) == 1; q += used) n++;
+  if (n != 21) {
+    fprintf(stderr, "--buffers: a case is 21 integers (%d read): %s\n", n, text);
+    return 2;
+  }
+  const bool trace = v[0] != 0, levels = v[9] != 0;
+  const int pre = (int)v[3], max_samples = (int)v[4];
+  BatchOpts o;
+  o.lv_batch = v[10], o.lv_stage_pct = v[11], o.lv_rec_pct = v[12], o.lv_floor = v[13], o.lv_streams = v[14];
+  o.lv_split = v[15], o.lv_hl_cap = v[16], o.lv_sort = v[17], o.lv_sort_from = v[18], o.lv_sort_copy = v[19];
+  o.lv_ray_bytes = v[20];
+  BatchItems it{1, 0, 0};
+  if (trace) it.n0 = trace_items(v[2], o);
+  else it = batch_items(v[1], pre, max_samples, o);
+  const BatchLayout L = batch_layout(
+      BatchIn{trace, levels, it.n0, it.parts, trace ? 0 : (size_t)v[2], (int)v[7], (int)v[8], (int)v[5], (int)v[6]}, o);
+  std::string why = L.refusal ? L.refusal : "-";
+  for (char& ch : why)
+    if (ch == ' ') ch = '_';
+  printf("sizeof_LevelCtl %zu parts %d batch_tiles %d n0 %zu refusal %s", sizeof(LevelCtl), it.parts, it.batch_tiles, it.n0,
+         why.c_str());
+  printf(" scap %zu slog2 %d lcap %zu hcap %zu hlog2 %d hlcap %zu rec_bytes %d sort_from %d sort_copy %d split %d ray_dbl %d",
+         L.scap, L.slog2, L.lcap, L.hcap, L.hlog2, L.hlcap, L.rec_bytes, L.sort_from, (int)L.sort_copy, (int)L.split,
+         L.ray_dbl);
+  for (int k = 0; k < LB_COUNT; k++)
+    printf(" off_%s %zu size_%s %zu present_%s %d", BATCH_BUF_NAMES[k], L.off[k], BATCH_BUF_NAMES[k], L.size[k],
+           BATCH_BUF_NAMES[k], (int)L.present[k]);
+  printf(" set %zu tail %zu total %zu\n", L.set, L.tail, L.total);
+  return 0;
+}
+
+// The cases: the arguments, one case each, or without arguments the lines of stdin.
+static int buffers(int n, char** cases) {
+  int rc = 0;
+  for (int k = 0; k < n && !rc; k++) rc = buffers_case(cases[k]);
+  char line[1024];
+  while (n == 0 && !rc && fgets(line, sizeof line, stdin))
+    if (line[strspn(line, " \t\r\n")]) rc = buffers_case(line);
+  return rc;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s world.yml [sah] | --plan world.yml...\n", argv[0]);
+    fprintf(stderr, "usage: %s world.yml [sah] | --plan world.yml... | --buffers [case...]\n", argv[0]);
     return 2;
   }
   if (!strcmp(argv[1], "--plan")) return plans(argc - 2, argv + 2);
+  if (!strcmp(argv[1], "--buffers")) return buffers(argc - 2, argv + 2);
   rtxcli::Scene sc;
   rtxcli::load_world(argv[1], sc);
   HostScene H;
