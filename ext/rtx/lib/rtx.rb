@@ -92,6 +92,8 @@ module RTX
   extern 'int rtx_render_at(void*, int, int, unsigned long long, void*)'
   extern 'int rtx_trace(void*, int, void*, void*, unsigned long long, void*)'
   extern 'int rtx_trace_device(void*, int, unsigned long long, void*, void*, void*, void*, void*)'
+  extern 'int rtx_render_pixels_device(void*, int, unsigned long long, void*, void*, void*, void*, void*)'
+  extern 'int rtx_render_pixels(void*, int, unsigned long long, void*, void*, void*, void*)'
   extern 'int rtx_path_trace(void*, int, void*, void*)'
   extern 'int rtx_quantize(void*, int, int, size_t, int, void*)'
   extern 'int rtx_quantize_device(void*, int, int, size_t, int, void*, void*)'

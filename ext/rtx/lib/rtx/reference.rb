@@ -185,6 +185,26 @@ module RTX
       { position: [x, @height - 1 - y], color: rgb[0, 24].unpack('d3') }
     end
 
+    # render_at for a list of pixels [[x, y], ...] in one call (rtx_render_pixels):
+    # an array of render_at's hashes, each with :variance, :samples and :status
+    # added; a raising pixel keeps its status (color NaN) instead of raising.
+    def render_pixels(list)
+      n = list.length
+      xy = Fiddle::Pointer[list.flatten.pack('l*')]
+      rgb = RTX.doubles(3 * n)
+      var = RTX.doubles(n)
+      info = Fiddle::Pointer.malloc(8 * [n, 1].max)
+      st = RTX.rtx_render_pixels(@rtx_ctx.ptr, n, @rtx_seed, xy, rgb, var, info)
+      inf = n.zero? ? [] : info[0, 8 * n].unpack('l*')
+      RTX.check(@rtx_ctx.ptr, st) if st != 0 && inf.each_slice(2).none? { |s, _| s != 0 }
+      colors = n.zero? ? [] : rgb[0, 24 * n].unpack('d*')
+      vars = n.zero? ? [] : var[0, 8 * n].unpack('d*')
+      list.each_with_index.map do |(x, y), i|
+        { position: [x, @height - 1 - y], color: colors[3 * i, 3], variance: vars[i],
+          samples: inf[2 * i + 1], status: inf[2 * i] }
+      end
+    end
+
     # Camera#render_sync (camera.rb:101-110): the whole frame in one call.
     def render_sync(file_path)
       buf = RTX.doubles(@width * @height * 3)

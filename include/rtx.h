@@ -427,6 +427,42 @@ rtx_status rtx_trace(rtx_context* ctx, int32_t n, const double* rays, const int3
 rtx_status rtx_trace_device(rtx_context* ctx, int32_t n, uint64_t seed, const double* d_rays,
                             const int32_t* d_keys, double* d_rgb, int32_t* d_status, void* hip_stream);
 
+/* Camera#render_at(x, y) (camera.rb:70-99) for a list of n pixels, with a status, the
+ * variance and the sample count per pixel.  Needs the scene and a camera.
+ *   d_xy:       int32[n][2] = x, y, render_at's own arguments: entry i is the pixel
+ *               rtx_render_at(ctx, x, y, ...) renders.  Any int32 values (lens_func checks no
+ *               bounds); duplicates are independent entries.  Required.
+ *   d_rgb:      double[n][3]; required; 8-byte alignment is enough.  The bits rtx_render writes
+ *               for that pixel, under every option.
+ *   d_variance: double[n] or NULL: the variance of camera.rb:80-85 after its division by
+ *               pre_sample_times, the value compared with variant_threshold.
+ *   d_info:     int32[n][2] or NULL = {status, samples}.  samples: the lens_func calls render_at
+ *               has made when it returns, pre_sample_times, or max_sample_times when the variance
+ *               test fired and max_sample_times > pre_sample_times (fired with max <= pre: the
+ *               colour is (mean * pre + 0) / max as in the reference, samples stays pre).
+ * A raising pixel: status is the rtx_status of the first raise in render_at's order (the raising
+ * pre sample of lowest index, else the raising extra sample of lowest index), samples that
+ * sample's index + 1, the colour three quiet NaNs, the variance a quiet NaN if a pre sample
+ * raised and the valid value if only an extra sample did.  Other pixels are unaffected.
+ * Like rtx_trace_device: asynchronous on hip_stream without a host synchronisation, nothing
+ * recorded in rtx_sync's state, RTX_OK whatever the statuses hold, the same rule for calls on one
+ * context (one thread; no overlap with another render or trace of the context unless the caller
+ * orders them).  n == 0 is RTX_OK; RTX_EINVAL for n < 0, a NULL context, d_xy or d_rgb, no scene
+ * or camera, or a camera whose ray stack exceeds 64 entries (as rtx_trace).
+ * The list is cut into chunks of P pixels, P * max(pre, max - pre) <= "lv_batch"; each chunk's
+ * pre samples, and then the extra samples of the pixels that take them, are one pass through
+ * rtx_trace_device's path.  "trace_engine" chooses each pass's engine as it does there, with
+ * "rays" read as the samples the pass is launched for (every pixel of the chunk, for the extras
+ * too: how many take them is known on the device only); "trace_engine_last" is the engine of
+ * the call's first pass.  rtx_level_stats afterwards is summed over both passes and all chunks
+ * (level 0: the samples traced through the bounce levels). */
+rtx_status rtx_render_pixels_device(rtx_context* ctx, int32_t n, uint64_t seed, const int32_t* d_xy,
+                                    double* d_rgb, double* d_variance, int32_t* d_info, void* hip_stream);
+/* The same with host buffers: fills them, and returns the status of the first raising pixel by
+ * index, named in rtx_last_error ("... at pixel i (x, y)"). */
+rtx_status rtx_render_pixels(rtx_context* ctx, int32_t n, uint64_t seed, const int32_t* xy,
+                             double* rgb, double* variance, int32_t* info);
+
 /* RayTracer#path_trace_sync(x, y, ray) for n rays (host buffers, rays as in
  * rtx_trace).  Never called by the reference, reproduced with its behaviour:
  * black below trace_depth 1 or on a miss, the highlight sum when a light's

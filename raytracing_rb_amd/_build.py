@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librtx.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("rtx_kernels.hip", "rtx_levels.hip", "rtx_aov.hip", "rtx_query.hip", "rtx_rtmap.hip",
-                                                "rtx_capi.cpp")]
+                                                "rtx_pixels.hip", "rtx_capi.cpp")]
 HEADERS = [os.path.join(CSRC, f) for f in ("rtx_scene.h", "rtx_vec3.h", "rtx_launch.h", "rtx_sched.h", "rtx_device.h", "rtx_bvh_build.h",
                                              "rtx_scene_build.h", "rtx_plan.h", "rtx_batch.h")] + [
     os.path.join(ROOT, "include", "rtx.h")]

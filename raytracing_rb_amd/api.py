@@ -149,6 +149,26 @@ class Camera:
         """Float64 framebuffer [H, W, 3], row = y (final image orientation)."""
         return self._r.render(x0, y0, x1, y1, seed=self.seed)
 
+    def render_pixels(self, xy, check=True):
+        """render_at for a list of pixels xy [n, 2] = (x, y) in one call: colours
+        [n, 3], the bits render() gives those pixels.  check=False: (rgb, variance,
+        status, samples) per pixel instead of RtxError for the first raising pixel
+        (Renderer.render_pixels)."""
+        return self._r.render_pixels(xy, seed=self.seed, check=check)
+
+    def sampling(self, x0=0, y0=0, x1=None, y1=None):
+        """The adaptive-sampling decision of render_at (camera.rb:78-96) for every
+        pixel of the region, row-major: (rgb [H, W, 3], variance [H, W], samples
+        int32 [H, W], status int32 [H, W]).  rgb has the bits of render() except at
+        raising pixels (status != 0), which are NaN there and fail render()."""
+        x1 = self.width if x1 is None else x1
+        y1 = self.height if y1 is None else y1
+        h, w = max(y1 - y0, 0), max(x1 - x0, 0)
+        ys, xs = np.mgrid[y0:y0 + h, x0:x0 + w]
+        xy = np.stack([xs.ravel(), ys.ravel()], axis=1).astype(np.int32)
+        rgb, var, status, samples = self._r.render_pixels(xy, seed=self.seed, check=False)
+        return rgb.reshape(h, w, 3), var.reshape(h, w), samples.reshape(h, w), status.reshape(h, w)
+
     def first_hit(self, sample=0, x0=0, y0=0, x1=None, y1=None):
         """The geometry passes next to the colour: lens_func(x, y, sample)
         (camera.rb:129-151) -> World#intersect (world.rb:37-59) for every pixel.

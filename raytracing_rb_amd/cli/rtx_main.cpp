@@ -16,6 +16,13 @@
 //                                             max_distance, 1)), out.albedo.png;
 //                                             quantized and blended like a colour
 //                                             frame (--no-blend applies)
+//   rtx a  out.png world.yml camera.yml      the adaptive-sampling map of the frame
+//                                             (rtx_render_pixels over every pixel,
+//                                             row-major): grey = 255 * samples /
+//                                             max(pre_sample_times, max_sample_times)
+//                                             (integer division), a raising pixel
+//                                             pure red; rows as the colour image,
+//                                             bytes written as they are (no blend)
 // options:
 //   --seed S             RNG seed (main.rb:10 seeds Random with 1; default 1)
 //   --device D           first GPU (default 0)
@@ -292,6 +299,35 @@ int main(int argc, char** argv) {
       check(c, rtx_first_hit(c, 0, 0, W, H, o.seed, 0, nullptr, geom.data()), "first_hit");
       rtx_context_destroy(c);
       write_geometry(o, geom, W, H, sc.desc.max_distance);
+      return 0;
+    }
+    if (o.mode == "a") {                                           // the sampling map of render_at
+      rtx_context* c = make_context(o.device, sc, cam);
+      for (const auto& kv : o.opt) check(c, rtx_set_option(c, kv.first.c_str(), kv.second), "option");
+      const size_t n = (size_t)W * H;
+      std::vector<int32_t> xy(n * 2), info(n * 2);
+      std::vector<double> rgb(n * 3);
+      for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+          xy[2 * ((size_t)y * W + x)] = x;
+          xy[2 * ((size_t)y * W + x) + 1] = y;
+        }
+      const rtx_status s = rtx_render_pixels(c, (int32_t)n, o.seed, xy.data(), rgb.data(), nullptr, info.data());
+      bool raised = false;
+      for (size_t i = 0; i < n; i++) raised = raised || info[2 * i] != 0;
+      if (s != RTX_OK && !raised) check(c, s, "render_pixels");   // (a raising pixel is painted, not fatal)
+      rtx_context_destroy(c);
+      const int ms = cam.pre_sample_times > cam.max_sample_times ? cam.pre_sample_times : cam.max_sample_times;
+      std::vector<uint8_t> rgba(n * 4);
+      for (size_t i = 0; i < n; i++) {
+        const uint8_t g = (uint8_t)(255 * info[2 * i + 1] / (ms > 0 ? ms : 1));
+        const bool bad = info[2 * i] != 0;
+        rgba[4 * i] = bad ? 255 : g;
+        rgba[4 * i + 1] = bad ? 0 : g;
+        rgba[4 * i + 2] = bad ? 0 : g;
+        rgba[4 * i + 3] = 255;
+      }
+      png_write_rgba8(o.out, rgba.data(), W, H);
       return 0;
     }
     const auto t0 = std::chrono::steady_clock::now();

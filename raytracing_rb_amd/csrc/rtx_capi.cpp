@@ -1581,20 +1581,47 @@ rtx_status rtx_render_at(rtx_context* c, int32_t x, int32_t y, uint64_t seed, do
 // One trace call on `stream`: the batch buffers (level_params, as a render's,
 // with "camera samples" read as "rays"; one part), then launch_trace_levels.
 // The staged records are always 96 B, whatever "lv_ray_bytes" says.
+// live / first: launch_trace_levels' (a ray count in device memory; the call's first trace resets the level
+// statistics).  ev0: the kernel-event pairs the call's earlier traces recorded.
 static rtx_status trace_levels(rtx_context* c, KParams& p, int maxs, bool levels, int32_t* d_status,
-                               hipStream_t stream) {
+                               hipStream_t stream, const int32_t* d_live = nullptr, bool first = true, int ev0 = 0) {
   const size_t n0 = trace_items(p.nrays, batch_opts(c));
   char* buf = nullptr;
   if (rtx_status s = level_params(c, p, context_layout(c, true, levels, n0, 1, 0), 1, stream, buf)) return s;
   // the levels' overflow re-trace keeps the render's grid cap; the lanes engine takes every resident workgroup
   p.lv_redo_blocks = levels ? (int32_t)c->opt_lv_redo_blocks : 0;
   KernelEvents kev;
-  if (rtx_status s = kernel_events(c, c->opt_kernel_events != 0, kev)) return s;
+  if (rtx_status s = kernel_events(c, c->opt_kernel_events != 0, kev)) {
+    hipFreeAsync(buf, stream);
+    return s;
+  }
+  kev.n = ev0;
   KernelEvents* const ke = c->opt_kernel_events ? &kev : nullptr;
   const hipError_t e = launch_trace_levels(p, levels ? levels_sph_mode(c, 0) : sph_mode(c), maxs,
                                            std::max(1, c->cam.depth), (int)n0, levels, d_status, stream, ke,
-                                           &c->last_plan);
+                                           &c->last_plan, d_live, first);
   return launched(c, e, ke, buf, stream);
+}
+
+// RayTracer#trace_sync for n explicit rays in device buffers through the engine "trace_engine" chooses
+// for a batch of n (rtx_trace_device; each pass of rtx_render_pixels_device).  p: prep()'s, with the
+// ray stacks (ensure_stack).  *ran_levels: the engine that ran.
+static rtx_status trace_pass(rtx_context* c, KParams p, int maxs, int32_t n, const double* d_rays,
+                             const int32_t* d_keys, double* d_rgb, int32_t* d_status, hipStream_t stream,
+                             bool* ran_levels, const int32_t* d_live = nullptr, bool first = true, int ev0 = 0) {
+  const bool want = c->opt_trace_engine == 1 || (c->opt_trace_engine == -1 && (int64_t)n >= RTX_TRACE_LEVELS_MIN_RAYS);
+  bool levels = want && levels_fit(c);
+  if (levels && c->opt_lv_split != 0 && c->scene.n_light <= LV_SPLIT_MAX_LIGHTS) {
+    if (c->opt_trace_engine == 1)
+      return fail(c, RTX_EINVAL, "lv_split 1: explicit rays run the fused level launches only");
+    levels = false;
+  }
+  p.rays = d_rays;
+  p.keys = d_keys;
+  p.nrays = n;
+  p.out = d_rgb;
+  *ran_levels = levels;
+  return trace_levels(c, p, maxs, levels, d_status, stream, d_live, first, ev0);
 }
 
 rtx_status rtx_trace_device(rtx_context* c, int32_t n, uint64_t seed, const double* d_rays, const int32_t* d_keys,
@@ -1612,18 +1639,8 @@ rtx_status rtx_trace_device(rtx_context* c, int32_t n, uint64_t seed, const doub
   int maxs = 0;
   if ((s = required_stack(c, maxs))) return s;
   if ((s = ensure_stack(c, p, maxs))) return s;
-  const bool want = c->opt_trace_engine == 1 || (c->opt_trace_engine == -1 && (int64_t)n >= RTX_TRACE_LEVELS_MIN_RAYS);
-  bool levels = want && levels_fit(c);
-  if (levels && c->opt_lv_split != 0 && c->scene.n_light <= LV_SPLIT_MAX_LIGHTS) {
-    if (c->opt_trace_engine == 1)
-      return fail(c, RTX_EINVAL, "lv_split 1: explicit rays run the fused level launches only");
-    levels = false;
-  }
-  p.rays = d_rays;
-  p.keys = d_keys;
-  p.nrays = n;
-  p.out = d_rgb;
-  if ((s = trace_levels(c, p, maxs, levels, d_status, (hipStream_t)stream))) return s;
+  bool levels = false;
+  if ((s = trace_pass(c, p, maxs, n, d_rays, d_keys, d_rgb, d_status, (hipStream_t)stream, &levels))) return s;
   c->last_trace_engine = levels ? 1 : 0;
   if (!levels) {                               // (rtx_level_stats, lv_plan_last: no level render)
     c->last_sort_levels = 0;
@@ -1666,6 +1683,123 @@ static rtx_status trace_host_levels(rtx_context* c, int32_t n, const double* ray
   const rtx_status r = (rtx_status)st[first];
   return fail(c, r, "%s at ray %llu%s", rtx_status_string(r), (unsigned long long)first,
               __builtin_popcount(kinds) > 1 ? " (and other errors)" : "");
+}
+
+// ------------------------------------------------------------------ pixel lists
+// Camera#render_at for the n pixels d_xy: the list in chunks of
+// P pixels with P * max(pre, max - pre) <= "lv_batch", so that each pass of a
+// chunk is one batch of the engine; per chunk the lens rays of the pre samples
+// (k_pixel_rays), their trace, render_at's pixel stage (k_pixel_reduce), and
+// with max > pre the extra samples of the pixels it listed: their rays
+// (k_pixel_extra_rays), a trace launched for the chunk's capacity whose live
+// ray count stays in device memory, and k_pixel_finish.  All on `stream`,
+// nothing read back.  The chunk buffers (rtx_launch.h PixelBufs) are one
+// stream-ordered allocation reused by every chunk, beside the engine's own.
+rtx_status rtx_render_pixels_device(rtx_context* c, int32_t n, uint64_t seed, const int32_t* d_xy, double* d_rgb,
+                                    double* d_variance, int32_t* d_info, void* hip_stream) {
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative pixel count");
+  if (n == 0) return RTX_OK;
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  if (!d_xy) return fail(c, RTX_EINVAL, "null pixel list");
+  if (!d_rgb) return fail(c, RTX_EINVAL, "null rgb buffer");
+  KParams p;
+  rtx_status s = prep(c, p, seed);
+  if (s) return s;
+  int maxs = 0;
+  if ((s = required_stack(c, maxs))) return s;
+  if ((s = ensure_stack(c, p, maxs))) return s;
+  const hipStream_t stream = (hipStream_t)hip_stream;
+  const int pre = p.pre, mx = p.max_samples, n_extra = std::max(0, mx - pre);
+  const int64_t per = std::max(pre, n_extra);
+  const int32_t P = (int32_t)std::max<int64_t>(1, std::min<int64_t>(n, c->opt_lv_batch / per));
+  const size_t cap = (size_t)P * (size_t)per;
+  const size_t rb = al256(cap * 6 * sizeof(double)), cb = al256(cap * 3 * sizeof(double)),
+               kb = al256(cap * 3 * sizeof(int32_t)), sb = al256(cap * sizeof(int32_t)),
+               lb = al256((size_t)P * sizeof(int32_t));
+  char* buf = nullptr;
+  HIPCHK(c, hipMallocAsync((void**)&buf, rb + cb + kb + sb + lb + 256, stream));
+  const PixelBufs b{(double*)buf, (int32_t*)(buf + rb + cb), (double*)(buf + rb), (int32_t*)(buf + rb + cb + kb),
+                    (int32_t*)(buf + rb + cb + kb + sb), (int32_t*)(buf + rb + cb + kb + sb + lb)};
+  hipError_t e = hipSuccess;
+  bool first = true, any_levels = false;
+  for (int32_t i0 = 0; i0 < n && e == hipSuccess && !s; i0 += P) {
+    const int32_t m = std::min(P, n - i0);
+    const int32_t* xy = d_xy + 2 * (size_t)i0;
+    double* rgb = d_rgb + 3 * (size_t)i0;
+    double* var = d_variance ? d_variance + i0 : nullptr;
+    int32_t* info = d_info ? d_info + 2 * (size_t)i0 : nullptr;
+    bool levels = false;
+    e = launch_pixel_rays(c->d_cam, seed, xy, m, pre, b, stream);
+    if (e != hipSuccess) break;
+    p.work = c->d_work + (c->work_seq++ % RTX_WORK_RING);
+    if ((s = trace_pass(c, p, maxs, m * pre, b.rays, b.keys, b.col, b.st, stream, &levels, nullptr, first,
+                        first ? 0 : c->n_ev)))
+      break;
+    if (first) c->last_trace_engine = levels ? 1 : 0;   // ("trace_engine_last": the engine of the call's first pass)
+    any_levels = any_levels || levels;
+    first = false;
+    e = launch_pixel_reduce(c->d_cam, m, pre, mx, b, rgb, var, info, stream);
+    if (e != hipSuccess || n_extra == 0) continue;
+    e = launch_pixel_extra_rays(c->d_cam, seed, xy, m, pre, mx, b, stream);
+    if (e != hipSuccess) break;
+    p.work = c->d_work + (c->work_seq++ % RTX_WORK_RING);
+    if ((s = trace_pass(c, p, maxs, m * n_extra, b.rays, b.keys, b.col, b.st, stream, &levels, b.count + 1, false,
+                        c->n_ev)))
+      break;
+    any_levels = any_levels || levels;
+    e = launch_pixel_finish(m, pre, mx, b, rgb, info, stream);
+  }
+  if (!any_levels) {                           // (rtx_level_stats, lv_plan_last: no level render)
+    c->last_sort_levels = 0;
+    c->last_plan = -1;
+  }
+  const hipError_t f = hipFreeAsync(buf, stream);
+  if (s) return s;
+  HIPCHK(c, e);
+  HIPCHK(c, f);
+  return RTX_OK;
+}
+
+// The host form: upload, rtx_render_pixels_device, download; the first raising
+// pixel by index is the call's status.
+rtx_status rtx_render_pixels(rtx_context* c, int32_t n, uint64_t seed, const int32_t* xy, double* rgb,
+                             double* variance, int32_t* info) {
+  if (!c) return RTX_EINVAL;
+  if (n < 0) return fail(c, RTX_EINVAL, "negative pixel count");
+  if (n == 0) return RTX_OK;
+  if (!c->have_scene || !c->have_cam) return fail(c, RTX_EINVAL, "no scene or camera uploaded");
+  if (!xy) return fail(c, RTX_EINVAL, "null pixel list");
+  if (!rgb) return fail(c, RTX_EINVAL, "null rgb buffer");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as trace_host_levels: wait for the context's earlier work (it may still read the scratch buffer
+  // that is reused and perhaps reallocated below) and discard the raises nobody collected
+  rtx_sync(c, nullptr);
+  const size_t N = (size_t)n, ob = N * 3 * sizeof(double), vb = N * sizeof(double), xb = N * 2 * sizeof(int32_t);
+  rtx_status s = ensure_scratch(c, ob + vb + 2 * xb + 64);
+  if (s) return s;
+  char* base = (char*)c->d_scratch;
+  double* d_rgb = (double*)base;
+  double* d_var = (double*)(base + ob);
+  int32_t* d_xy = (int32_t*)(base + ob + vb);
+  int32_t* d_info = (int32_t*)(base + ob + vb + xb);
+  HIPCHK(c, hipMemcpy(d_xy, xy, xb, hipMemcpyHostToDevice));
+  if ((s = rtx_render_pixels_device(c, n, seed, d_xy, d_rgb, variance ? d_var : nullptr, d_info, nullptr))) return s;
+  std::vector<int32_t> st;
+  int32_t* inf = info;
+  if (!inf) {
+    st.resize(2 * N);
+    inf = st.data();
+  }
+  HIPCHK(c, hipMemcpy(rgb, d_rgb, ob, hipMemcpyDeviceToHost));
+  if (variance) HIPCHK(c, hipMemcpy(variance, d_var, vb, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(inf, d_info, xb, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < N; i++)
+    if (inf[2 * i]) {
+      const rtx_status r = (rtx_status)inf[2 * i];
+      return fail(c, r, "%s at pixel %zu (%d, %d)", rtx_status_string(r), i, xy[2 * i], xy[2 * i + 1]);
+    }
+  return RTX_OK;
 }
 
 rtx_status rtx_trace(rtx_context* c, int32_t n, const double* rays, const int32_t* keys, uint64_t seed,

@@ -158,8 +158,37 @@ hipError_t launch_redo_rays(const KParams& q, int mode, int maxs, int n, hipStre
 // status int32[n] (or null), in batches of `batch` rays.  levels: through the bounce
 // levels (the lv_* buffers of `p` sized for `batch` level-0 items, 96-B staged records, no split phases);
 // else every ray through the lanes engine (lv_ctl and the lv_redo_* buffers only).  Nothing goes to p.err.
+// live: null, or the number of rays that exist, in device memory (<= p.nrays, the capacity the launches are
+// sized for): slots at or past it are padding, with no tree, no status and no colour written.  first false:
+// the call adds to the level statistics of the calls before it instead of resetting them.
 hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batch, bool levels, int32_t* status,
-                               hipStream_t s, KernelEvents* kev = nullptr, int64_t* plan_out = nullptr);
+                               hipStream_t s, KernelEvents* kev = nullptr, int64_t* plan_out = nullptr,
+                               const int32_t* live = nullptr, bool first = true);
+// Camera#render_at for a list of pixels (rtx_render_pixels, DESIGN.md §3.23, rtx_pixels.hip).  One chunk's
+// buffers: rays [cap][6], keys int32[cap][3], the traced samples' colours col [cap][3] and statuses st
+// int32[cap] (cap = pixels x max(pre, max - pre)), the pixels taking extra samples list int32[pixels] and
+// count int32[2] = {listed pixels, their extra samples}.
+struct PixelBufs {
+  double* rays;
+  int32_t* keys;
+  double* col;
+  int32_t* st;
+  int32_t* list;
+  int32_t* count;
+};
+// The lens rays and keys (x, y, j), j < pre, of the npx pixels d_xy, item (pixel, sample); zeroes the count.
+hipError_t launch_pixel_rays(const CameraDev* cam, uint64_t seed, const int32_t* d_xy, int npx, int pre,
+                             const PixelBufs& b, hipStream_t s);
+// render_at's pixel stage over the traced pre samples (col, st): rgb [npx][3], variance [npx] or null, info
+// int32[npx][2] = {status, samples} or null; the pixels whose variance asks for extra samples are listed.
+hipError_t launch_pixel_reduce(const CameraDev* cam, int npx, int pre, int max_samples, const PixelBufs& b,
+                               double* d_rgb, double* d_variance, int32_t* d_info, hipStream_t s);
+// The rays and keys (x, y, j), j = pre .. max - 1, of the listed pixels, item (list entry, sample); count[1].
+hipError_t launch_pixel_extra_rays(const CameraDev* cam, uint64_t seed, const int32_t* d_xy, int npx, int pre,
+                                   int max_samples, const PixelBufs& b, hipStream_t s);
+// The listed pixels' colours from the pre mean parked in d_rgb and the traced extra samples (col, st).
+hipError_t launch_pixel_finish(int npx, int pre, int max_samples, const PixelBufs& b, double* d_rgb, int32_t* d_info,
+                               hipStream_t s);
 int read_level_stamps(unsigned long long* out, int reset);   // diagnostic builds
 hipError_t launch_quantize(const double* rgb, int w, int h, size_t stride, int blend, uint8_t* out,
                            hipStream_t s);

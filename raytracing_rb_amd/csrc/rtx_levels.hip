@@ -649,7 +649,9 @@ __device__ __forceinline__ bool lv_walk(const KParams& p, char* lds, bool ext, V
 // items of one level-0 chunk (the first half of the level kernels), see decode_item.
 // SRC: what a level-0 item is.  LSRC_CAMERA: a camera sample (renders).
 // LSRC_RAYS: ray `idx` of an explicit batch (rtx_trace_device):
-// p.rays[idx] with the RNG key p.keys[idx]; items past p.nrays are padding.
+// p.rays[idx] with the RNG key p.keys[idx]; items at or past the batch's live
+// count are padding (lv_ctl->count0: p.nrays, or less when the call gave a
+// count in device memory, k_trace_live).
 // Only the level-0 kernels of a trace call are instantiated for it
 // (k_level / k_level_c <..., LSRC_RAYS>, picked by launch_level_bs): every
 // other kernel compiles from LSRC_CAMERA.
@@ -676,7 +678,7 @@ __device__ __forceinline__ void lv_ray(const KParams& p, int level, uint32_t idx
   if (level == 0) {
     if constexpr (SRC == LSRC_RAYS) {
       root = (int)idx;
-      valid = idx < (uint32_t)p.nrays;
+      valid = idx < p.lv_ctl->count0;
       if (valid) {
         lv_ray_explicit(p, idx, cur.ray, x, y, sample);
         cur.att = v3(1.0, 1.0, 1.0);
@@ -1695,6 +1697,8 @@ __global__ __launch_bounds__(256) void k_tree_finalize_extra(KParams p, int nlev
 // ray's colour is three quiet NaNs.  Nothing goes to p.err.  Same walk stack
 // as k_tree_finalize (LDS up to 16 levels, private above).  nlev 0: no level
 // ran, every ray was listed (the lanes engine through this entry point).
+// The batch's rays are its live count (lv_ctl->count0 <= p.nrays): a slot past
+// it has no tree and no listed record, and nothing is written for it.
 template <int SD>
 __global__ __launch_bounds__(256) void k_trace_finalize(KParams p, int nlev, int32_t* status) {
   __shared__ uint32_t base[LV_MAXL + 1];
@@ -1704,7 +1708,8 @@ __global__ __launch_bounds__(256) void k_trace_finalize(KParams p, int nlev, int
   uint32_t* lo = lds_fin + nlev * 64 + threadIdx.x;
   uint32_t* hi = lo + SD * 256;
   uint32_t lo_p[SD > 16 ? LV_MAXL : 1], hi_p[SD > 16 ? LV_MAXL : 1];
-  for (int i = blockIdx.x * 256 + (int)threadIdx.x; i < p.nrays; i += (int)gridDim.x * 256) {
+  const int n = (int)p.lv_ctl->count0;
+  for (int i = blockIdx.x * 256 + (int)threadIdx.x; i < n; i += (int)gridDim.x * 256) {
     uint32_t e = 0, nv = 0;
     V3 c = SD > 16 ? lv_sample(p, base, pex, i, nlev, lo_p, hi_p, 1, LV_MAXL, e, nv)
                    : lv_sample(p, base, pex, i, nlev, lo, hi, 256, SD, e, nv);
@@ -1718,13 +1723,27 @@ __global__ __launch_bounds__(256) void k_trace_finalize(KParams p, int nlev, int
 }
 
 // The lanes engine through rtx_trace_device: every ray of the batch is listed
-// for the re-render (k_level_begin has zeroed the list).
+// for the re-render (k_level_begin has zeroed the list): the live ones.
 __global__ __launch_bounds__(256) void k_trace_list_all(KParams p) {
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
-  if (i == 0) p.lv_ctl->redo_n = (uint32_t)p.nrays;
-  if (i >= p.nrays) return;
+  const int n = (int)p.lv_ctl->count0;
+  if (i == 0) p.lv_ctl->redo_n = (uint32_t)n;
+  if (i >= n) return;
   p.lv_redo_of[i] = i;
   p.lv_redo_list[i] = i;
+}
+
+// A trace batch whose ray count lives in device memory (rtx_render_pixels'
+// extra samples): after k_level_begin, the batch's level-0 items become the
+// rays of *live that fall into it, [b0, b0 + p.nrays), instead of its
+// capacity p.nrays.  Level 0, the listing and the reduction read count0; the
+// launches stay sized for the capacity and their empty chunks leave at once.
+__global__ void k_trace_live(KParams p, const int32_t* live, int b0) {
+  if (blockIdx.x || threadIdx.x) return;
+  const long left = (long)*live - (long)b0;
+  const uint32_t v = left <= 0 ? 0u : left < (long)p.nrays ? (uint32_t)left : (uint32_t)p.nrays;
+  p.lv_ctl->count0 = v;
+  p.lv_ctl->lay_base[1] = v;
 }
 
 // The batch's deferred highlight rays (lv_hl_defer): each thread re-runs
@@ -2238,6 +2257,8 @@ struct LevelBatch {
   int step = 0;
   bool rays = false;               // a trace call's batch: n0_max explicit rays (q.rays, q.keys, q.nrays), results to
   int32_t* tr_status = nullptr;    // q.out and tr_status (k_trace_finalize)
+  const int32_t* live = nullptr;   // a trace call's ray count in device memory (k_trace_live), rays from live_b0 on
+  int live_b0 = 0;
   bool done() const { return step > nlev + 1; }
   hipError_t run() {                 // every step, in order
     hipError_t e = hipSuccess;
@@ -2250,6 +2271,7 @@ struct LevelBatch {
       const int words = std::min(nlev + 1, LV_MAXL + 1) * LV_SLICES * 32;
       hipLaunchKernelGGL(k_level_begin, dim3((unsigned)std::min(64, (words + 255) / 256)), dim3(256), 0, s, q, n0_max,
                          first ? 1 : 0, nlev);
+      if (live) hipLaunchKernelGGL(k_trace_live, dim3(1), dim3(64), 0, s, q, live, live_b0);
       e = hipGetLastError();
       if (e == hipSuccess && after_begin) e = hipEventRecord(after_begin, s);
     } else if (step <= nlev) {
@@ -2362,8 +2384,11 @@ hipError_t launch_levels(KParams p, int mode, int maxs, int nlev, int batch_tile
 // batch (no plan is recorded).  The lv_* buffers of `p` are the caller's, sized
 // for `batch` level-0 items as launch_levels'; the records staged are 96 B
 // (p.lv_ray_dbl = 12).
+// live: null, or the rays that exist, counted in device memory (at most p.nrays,
+// which stays the capacity every launch is sized for).  first: the call's
+// first batch resets the level statistics (false: this call adds to them).
 hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batch, bool levels, int32_t* status,
-                               hipStream_t s, KernelEvents* kev, int64_t* plan_out) {
+                               hipStream_t s, KernelEvents* kev, int64_t* plan_out, const int32_t* live, bool first) {
   if (p.nrays <= 0) return hipSuccess;
   if (levels && (p.lv_split || p.lv_ray_dbl != RAY_DOUBLES)) return hipErrorInvalidValue;
   begin_call(p, mode);
@@ -2379,13 +2404,16 @@ hipError_t launch_trace_levels(KParams p, int mode, int maxs, int nlev, int batc
     q.out = whole.out + (size_t)b0 * 3;
     int32_t* st = status ? status + b0 : nullptr;
     if (levels) {
-      LevelBatch b{q, mode, maxs, nlev, q.nrays, 0, s, kev, b0 == 0, nullptr, &plan};
+      LevelBatch b{q, mode, maxs, nlev, q.nrays, 0, s, kev, first && b0 == 0, nullptr, &plan};
       b.rays = true;
       b.tr_status = st;
+      b.live = live;
+      b.live_b0 = b0;
       e = b.run();
       continue;
     }
-    hipLaunchKernelGGL(k_level_begin, dim3(1), dim3(256), 0, s, q, q.nrays, b0 == 0 ? 1 : 0, 0);
+    hipLaunchKernelGGL(k_level_begin, dim3(1), dim3(256), 0, s, q, q.nrays, first && b0 == 0 ? 1 : 0, 0);
+    if (live) hipLaunchKernelGGL(k_trace_live, dim3(1), dim3(64), 0, s, q, live, b0);
     hipLaunchKernelGGL(k_trace_list_all, dim3((unsigned)((q.nrays + 255) / 256)), dim3(256), 0, s, q);
     e = hipGetLastError();
     if (e == hipSuccess) e = launch_redo_rays(q, mode, maxs, q.nrays, s);

@@ -89,6 +89,26 @@ class Renderer:
         self._check(self.lib.rtx_render_at(self.h, x, y, seed, _dp(out)))
         return out
 
+    def render_pixels(self, xy, seed=1, check=True):
+        """Camera#render_at for the pixels xy int32 [n, 2] = (x, y) in one call
+        (rtx_render_pixels): colours [n, 3] with the bits render() gives those
+        pixels.  Any int32 coordinates; duplicates are independent entries.
+        check=True raises RtxError for the first raising pixel by index.
+        check=False returns (rgb, variance [n], status int32 [n], samples int32
+        [n]): the variance render_at compares with variant_threshold, every
+        pixel's own rtx_status and the lens_func calls render_at made for it; a
+        raising pixel's colour is NaN (its variance too if a pre sample raised)."""
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        n = len(xy)
+        rgb = np.empty((n, 3), np.float64)
+        var = np.empty(n, np.float64)
+        info = np.zeros((n, 2), np.int32)
+        st = self.lib.rtx_render_pixels(self.h, n, seed, C.c_void_p(xy.ctypes.data), C.c_void_p(rgb.ctypes.data),
+                                        C.c_void_p(var.ctypes.data), C.c_void_p(info.ctypes.data))
+        if st and (check or not info[:, 0].any()):   # (a status without a raising pixel: an argument or HIP error)
+            self._check(st)
+        return rgb if check else (rgb, var, info[:, 0].copy(), info[:, 1].copy())
+
     def trace(self, rays, keys, seed=1, check=True):
         """RayTracer#trace_sync for rays [n, 6] = (front, position) with the RNG keys
         [n, 3] = (x, y, sample) (rtx_trace) -> colours [n, 3].  check=True raises
@@ -309,6 +329,25 @@ class Renderer:
         self._check(self.lib.rtx_trace_device(self.h, n, seed, C.c_void_p(ptr(d_rays)), C.c_void_p(ptr(d_keys)),
                                               C.c_void_p(ptr(d_rgb)), C.c_void_p(ptr(d_status)),
                                               C.c_void_p(stream or 0)))
+
+    def render_pixels_device(self, d_xy, d_rgb, d_variance=None, d_info=None, seed=1, stream=None, n=None):
+        """rtx_render_pixels_device: d_xy int32 [n, 2], d_rgb float64 [n, 3], d_variance
+        None or float64 [n], d_info None or int32 [n, 2] = (status, samples): torch
+        tensors on this renderer's device (n = rows of d_xy) or raw device pointers
+        with n given.  Asynchronous on `stream`; raises go to d_info only, a raising
+        pixel's colour is NaN."""
+        def ptr(t):
+            return 0 if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+        if n is None:
+            if not hasattr(d_xy, "numel"):
+                raise ValueError("raw device pointers need n")
+            n = d_xy.numel() // 2
+            for t, per in ((d_rgb, 3), (d_variance, 1), (d_info, 2)):
+                if t is not None and hasattr(t, "numel") and t.numel() < n * per:
+                    raise ValueError("a buffer is smaller than the %d pixels need" % n)
+        self._check(self.lib.rtx_render_pixels_device(self.h, n, seed, C.c_void_p(ptr(d_xy)), C.c_void_p(ptr(d_rgb)),
+                                                      C.c_void_p(ptr(d_variance)), C.c_void_p(ptr(d_info)),
+                                                      C.c_void_p(stream or 0)))
 
     def rows_per_rank(self, tile_rows, nranks):
         return self.lib.rtx_tiles_rows_per_rank(self.height, tile_rows, nranks)
